@@ -12,6 +12,14 @@ gradient when N > 1] -> global-norm gradient clipping (1.0) -> AdamW
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2_l1|c4|c5]
                        [--scaling weak|strong] [--path step|module] [--precision highest|high|medium]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, captures the step, runs the untimed eager and warm-up steps, times K steps
+and prints the result line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also
+writes what the last timed step computed (loss, logits, gradients, updated parameters, ...) as
+DIR/<name>.npy: the inputs and weights are seeded, so two builds run with the same arguments can be
+compared array for array.  --full adds what takes passes of its own: the kernel-level profile
+(per-kernel and per-stage times, the dominant kernel's roofline), the per-step spread (median,
+p10 / p90) and the CPU baseline.
 N > 1: one process per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) the
 ranks join directly; a plain `python bench.py --gpus N` starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a CHILD process
@@ -212,6 +220,49 @@ def make_inputs(w, B, seed, device):
     return [f.to(device) for f in feats], mask.to(device), labels.to(device)
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20    # --dump-outputs: all arrays together stay under 64 MB
+
+
+def step_outputs(trainer):
+    """What a caller of the timed path holds after a step, by name: the loss, the logits and fusion
+    weights (fused step), the pre-clip gradient norm, the flat gradient, the input gradients and
+    the flat parameters after the update."""
+    if isinstance(trainer, ModuleRunner):
+        out = {"loss": trainer.loss, "grad_norm": trainer.trainer.grad_norm, "params": trainer.trainer.flat.flat}
+        out.update({f"dx{i}": f.grad for i, f in enumerate(trainer.feats) if f.grad is not None})
+        return out
+    out = {"loss": trainer.loss, "logits": trainer.logits, "fusion_weights": trainer.fw,
+           "grad_norm": trainer.grad_norm, "grad": trainer.grad, "params": trainer.flat}
+    out.update({f"dx{i}": t for i, t in enumerate(trainer.dx)})
+    return out
+
+
+def snapshot_outputs(outputs, budget=DUMP_BUDGET_BYTES):
+    """Host float32 copies of the outputs within `budget` bytes in all.  The budget is shared
+    smallest array first: an array within its share is kept whole, a larger one is cut to a fixed
+    sample of its flattened elements (indices drawn with replacement from a generator seeded by the
+    array's position in name order and its size, so two builds sample the same elements)."""
+    order = sorted(outputs, key=lambda k: (outputs[k].numel(), k))
+    left, arrays = budget, {}
+    for i, name in enumerate(order):
+        t = outputs[name].detach().reshape(-1).float()
+        share = left // (len(order) - i) // 4
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(1000003 * sorted(outputs).index(name) + t.numel())
+            idx = torch.randint(0, t.numel(), (share,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        arrays[name] = t.cpu().numpy().reshape(outputs[name].shape if t.numel() == outputs[name].numel() else -1)
+        left -= 4 * t.numel()
+    return arrays
+
+
+def write_outputs(arrays, directory):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def _cpu_leg(w, bs, threads, budget_s, max_steps):
     """Oracle train steps (fwd + CE + bwd, dropout 0.1) at `threads` threads for ~budget_s."""
     from oracle.hybrid_cpu import hybrid_train_step
@@ -312,13 +363,19 @@ def main(argv=None):
                          "instead of the default opaque module")
     ap.add_argument("--dropout", type=float, default=0.1,
                     help="diagnostics only: the benchmark workload is dropout 0.1")
-    ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the kernel-level profile (per-kernel and per-stage times, "
+                         "the dominant kernel's roofline), the per-step spread pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (step_outputs) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (rank 0)")
+    ap.add_argument("--skip-cpu", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--profile-steps", type=int, default=30,
-                    help="eager steps of the kernel-level profile pass (untimed; after the capture, right "
-                         "before the warm-up: they also bring the GPU to its steady clocks)")
+                    help="untimed eager steps after the capture, right before the warm-up: they bring the GPU "
+                         "to its steady clocks; under --full they are the kernel-level profile pass")
     ap.add_argument("--dump-launches", default=None,
-                    help="write every profiled launch (stage, kernel, ms, flops, bytes) of the last profile step "
-                         "to this JSON file")
+                    help="--full: write every profiled launch (stage, kernel, ms, flops, bytes) of the last "
+                         "profile step to this JSON file")
     ap.add_argument("--precision", default="highest", choices=["highest", "high", "medium"],
                     help="torch.set_float32_matmul_precision for the run: 'highest' = fp32 MFMA (the "
                          "fp32-parity headline), 'high' = bf16x3 (operands split into bf16 hi + lo, "
@@ -327,6 +384,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_launches and not args.full:
+        raise SystemExit("--dump-launches needs --full (the kernel-level profile pass)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: torch.distributed.run as a child, started before this process
         # touches the GPU (never an exec from a GPU-initialised process)
@@ -377,38 +438,43 @@ def main(argv=None):
 
     # the graph is captured first: its host work (about 17 ms at C2) leaves the GPU idle, and the
     # GPU's clocks then take ~30 ms of sustained load to ramp back up (kernel trace of
-    # the driver's command, profiles/r06/timed_gap/).  The kernel-level profile pass that follows
-    # keeps the GPU busy right up to the warm-up, so the timed region starts at the steady-state
-    # rate a training loop runs at after its first few tens of milliseconds.
+    # the driver's command, profiles/r06/timed_gap/).  The eager steps that follow (under --full
+    # the kernel-level profile pass) keep the GPU busy right up to the warm-up, so the timed
+    # region starts at the steady-state rate a training loop runs at after its first few tens
+    # of milliseconds.
     # (the launch-lean L = 1 step runs eagerly: HybridTrainStep.replay_pays)
     graph = args.path == "step" and not args.no_graph and trainer.replay_pays()
     if graph:
         trainer.capture()
 
-    # kernel-level timing (eager): hipEvents around each launch group and each
-    # kernel launch, on the launch stream (mmf_profile_begin/end)
-    # (the compiled path's profile steps run its module eagerly: the same library launches,
+    # --full: kernel-level timing of those eager steps, hipEvents around each launch group and
+    # each kernel launch, on the launch stream (mmf_profile_begin/end).  A plain run takes the
+    # same steps unprofiled: the same GPU work ahead of the timed region, and the same dropout
+    # stream position in it, with or without --full
+    # (the compiled path's eager steps run its module eagerly: the same library launches,
     # outside the graphs the compiled module captures)
     prof_fb = (lambda: trainer.forward_backward(eager=True)) if isinstance(trainer, ModuleRunner) \
         else trainer.forward_backward
     prof_fb()
     torch.cuda.synchronize(dev)
-    mmf_native.profile_begin()
+    if args.full:
+        mmf_native.profile_begin()
     for _ in range(args.profile_steps):
         prof_fb()
-    stages, launches = mmf_native.profile_end()
-    if args.dump_launches and rank == 0:
-        per = len(launches) // max(1, args.profile_steps)
-        with open(args.dump_launches, "w") as f:
-            json.dump([{"stage": st_, "kernel": k_, "ms": ms_, "gflop": fl_ / 1e9, "mb": by_ / 1e6,
-                        "tflops": fl_ / (ms_ * 1e-3) / 1e12 if ms_ > 0 else None}
-                       for st_, k_, ms_, fl_, by_ in launches[-per:]], f, indent=1)
-    per_stage = {}
-    for name, ms in stages:
-        t, n = per_stage.get(name, (0.0, 0))
-        per_stage[name] = (t + ms, n + 1)
-    avg_ms = {k: t / n for k, (t, n) in per_stage.items()}
-    kernels = kernel_table(launches, args.profile_steps)
+    if args.full:
+        stages, launches = mmf_native.profile_end()
+        if args.dump_launches and rank == 0:
+            per = len(launches) // max(1, args.profile_steps)
+            with open(args.dump_launches, "w") as f:
+                json.dump([{"stage": st_, "kernel": k_, "ms": ms_, "gflop": fl_ / 1e9, "mb": by_ / 1e6,
+                            "tflops": fl_ / (ms_ * 1e-3) / 1e12 if ms_ > 0 else None}
+                           for st_, k_, ms_, fl_, by_ in launches[-per:]], f, indent=1)
+        per_stage = {}
+        for name, ms in stages:
+            t, n = per_stage.get(name, (0.0, 0))
+            per_stage[name] = (t + ms, n + 1)
+        avg_ms = {k: t / n for k, (t, n) in per_stage.items()}
+        kernels = kernel_table(launches, args.profile_steps)
 
     for _ in range(args.warmup):
         trainer.step()
@@ -429,28 +495,28 @@ def main(argv=None):
     dt = float(dt_t.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
-    # the per-step spread (median, p10 / p90): a separate pass after the timed region with one event
-    # per step on the stream the steps run on -- an event recorded between graph replays costs
-    # ~5 us of GPU time per step on this stack (scripts/replay_gap_probe.py), so the timed region
-    # above has none
-    n_spread = min(args.steps, 50)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_spread + 1)]
-    for i in range(n_spread):
-        evs[i].record()
-        trainer.step()
-    evs[-1].record()
-    torch.cuda.synchronize(dev)
-    per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_spread))
-    med = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] +
-                                                                          per_step[len(per_step) // 2])
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before any later pass steps over them
+        write_outputs(snapshot_outputs(step_outputs(trainer)), args.dump_outputs)
+    if args.full:
+        # the per-step spread (median, p10 / p90): a separate pass after the timed region with one event
+        # per step on the stream the steps run on -- an event recorded between graph replays costs
+        # ~5 us of GPU time per step on this stack (scripts/replay_gap_probe.py), so the timed region
+        # above has none
+        n_spread = min(args.steps, 50)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_spread + 1)]
+        for i in range(n_spread):
+            evs[i].record()
+            trainer.step()
+        evs[-1].record()
+        torch.cuda.synchronize(dev)
+        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_spread))
+        med = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] +
+                                                                              per_step[len(per_step) // 2])
     loss = float(trainer.loss.item())
 
     if rank == 0:
-        roofline = dominant_roofline(kernels, args.workload, args.precision)
         step_fl = total_step_flops(wr)
-        cpu = None
-        if world == 1 and not args.skip_cpu:
-            cpu = cpu_baseline(w)
         Ls = w["L"]
         lens = Ls[0] if len(set(Ls)) == 1 else Ls
         mask_note = "" if w["keep"] >= 1 else f", modality masks keep={w['keep']} (+1% all-masked rows)"
@@ -479,22 +545,28 @@ def main(argv=None):
                        "global_batch": B * world, "per_gpu_batch": B, "seq_len": lens or 1,
                        "parallelism": f"dp{world}", "path": args.path + ("+traceable" if args.traceable else ""),
                        "graph": graph, "matmul_precision": args.precision},
-            "ms_per_step_median": round(med, 4),
-            "ms_per_step_spread_source": f"a separate pass of {n_spread} event-timed steps after the timed region",
-            "ms_per_step_p10_p90": [round(per_step[len(per_step) // 10], 4),
-                                    round(per_step[min(len(per_step) - 1, (9 * len(per_step)) // 10)], 4)],
-            "roofline": roofline,
-            "cpu_baseline": cpu,
             "step_tflops_algorithmic": round(step_fl / (ms_per_step * 1e-3) / 1e12, 3),
             "step_gflop_algorithmic": round(step_fl / 1e9, 2),
-            "step_gflop_executed_plan": round(sum(v["flops_per_launch"] * v["launches_per_step"]
-                                                  for v in kernels.values()) / 1e9, 2),
-            "stage_ms": {k: round(v, 4) for k, v in sorted(avg_ms.items(), key=lambda kv: -kv[1])},
-            "kernels": {k: {kk: v[kk] for kk in ("ms_per_step", "launches_per_step", "avg_launch_ms",
-                                                 "bound", "achieved", "unit", "frac", "mfma_frac", "hbm_frac")}
-                        for k, v in list(kernels.items())[:12]},
             "loss": round(loss, 5),
         }
+        if args.full:
+            cpu = None
+            if world == 1 and not args.skip_cpu:
+                cpu = cpu_baseline(w)
+            out.update({
+                "ms_per_step_median": round(med, 4),
+                "ms_per_step_spread_source": f"a separate pass of {n_spread} event-timed steps after the timed region",
+                "ms_per_step_p10_p90": [round(per_step[len(per_step) // 10], 4),
+                                        round(per_step[min(len(per_step) - 1, (9 * len(per_step)) // 10)], 4)],
+                "roofline": dominant_roofline(kernels, args.workload, args.precision),
+                "cpu_baseline": cpu,
+                "step_gflop_executed_plan": round(sum(v["flops_per_launch"] * v["launches_per_step"]
+                                                      for v in kernels.values()) / 1e9, 2),
+                "stage_ms": {k: round(v, 4) for k, v in sorted(avg_ms.items(), key=lambda kv: -kv[1])},
+                "kernels": {k: {kk: v[kk] for kk in ("ms_per_step", "launches_per_step", "avg_launch_ms",
+                                                     "bound", "achieved", "unit", "frac", "mfma_frac", "hbm_frac")}
+                            for k, v in list(kernels.items())[:12]},
+            })
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

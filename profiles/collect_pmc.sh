@@ -7,7 +7,7 @@ OUT=${1:-gpurun_out/pmc}
 shift || true
 export TMPDIR=/tmp
 mkdir -p "$OUT"
-B="python3 bench.py --steps 2 --warmup 1 --skip-cpu --no-graph --profile-steps 1 $*"
+B="python3 bench.py --full --steps 2 --warmup 1 --skip-cpu --no-graph --profile-steps 1 $*"
 pass() {
   local name=$1; shift
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o run -- $B \

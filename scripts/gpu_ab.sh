@@ -19,7 +19,7 @@ for i in $(seq 1 "$R"); do
         IFS=',' read -ra kv <<< "$envs"
         for e in "${kv[@]}"; do export "$e"; done
       fi
-      timeout -k 10 300 python -u bench.py "$@" > "$O/${label}_$i.json" 2> "$O/${label}_$i.err"
+      timeout -k 10 300 python -u bench.py --full "$@" > "$O/${label}_$i.json" 2> "$O/${label}_$i.err"
     ) || { echo "arm $label run $i failed"; exit 1; }
     echo "$label $i $(python3 -c "import json,sys;d=json.loads(open('$O/${label}_$i.json').read().strip().splitlines()[-1]);print(d['ms_per_step'],d['ms_per_step_median'])")"
   done

@@ -13,8 +13,8 @@ mkdir -p $O
 i=0
 for L in "${LIBS[@]}"; do
   i=$((i+1))
-  MMF_LIB_PATH=$PWD/$L timeout -k 10 300 python -u bench.py --steps 50 --warmup 10 --skip-cpu "$@" > $O/bench_$i.json 2> $O/bench_$i.err || exit 1
-  MMF_LIB_PATH=$PWD/$L timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$i -o run -- python3 bench.py --steps 30 --warmup 5 --skip-cpu "$@" > $O/prof_$i.json 2> $O/prof_$i.err || exit 1
+  MMF_LIB_PATH=$PWD/$L timeout -k 10 300 python -u bench.py --full --steps 50 --warmup 10 --skip-cpu "$@" > $O/bench_$i.json 2> $O/bench_$i.err || exit 1
+  MMF_LIB_PATH=$PWD/$L timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$i -o run -- python3 bench.py --full --steps 30 --warmup 5 --skip-cpu "$@" > $O/prof_$i.json 2> $O/prof_$i.err || exit 1
   python3 - "$O" "$i" "$L" <<'EOF'
 import csv, glob, json, sys
 o, i, lib = sys.argv[1:4]

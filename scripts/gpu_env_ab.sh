@@ -20,7 +20,7 @@ for i in 1 2; do
     [ $v = serial ] && export MMF_KW_SERIAL=1
     [ $v = side ] && export MMF_SIDE_STREAM=1
     [ $v = pstore ] && export MMF_PSTORE=1
-    timeout -k 10 300 python -u bench.py --workload ${WORKLOAD:-c2} --precision ${PRECISION:-highest} --steps ${STEPS:-50} --warmup 10 --skip-cpu > $O/${WORKLOAD:-c2}_${v}_$i.json 2> $O/${WORKLOAD:-c2}_${v}_$i.err || exit 1
+    timeout -k 10 300 python -u bench.py --full --workload ${WORKLOAD:-c2} --precision ${PRECISION:-highest} --steps ${STEPS:-50} --warmup 10 --skip-cpu > $O/${WORKLOAD:-c2}_${v}_$i.json 2> $O/${WORKLOAD:-c2}_${v}_$i.err || exit 1
     echo "$v $i ok"
   done
 done

@@ -11,14 +11,14 @@ C=multimodal-sensor-fusion-with-attention-rajeevatla_amd/csrc
 for i in 1 2; do
   for v in "$@"; do
     if [ $v = cur ]; then unset MMF_LIB_PATH; else export MMF_LIB_PATH=$GRAFT_REPO_ROOT/$C/libmmfusion_$v.so; fi
-    timeout -k 10 300 python -u bench.py --workload c5 --precision medium --steps 30 --warmup 10 --skip-cpu > $O/c5m_${v}_$i.json 2> $O/c5m_${v}_$i.err || exit 1
-    timeout -k 10 300 python -u bench.py --workload c2 --steps 50 --warmup 10 --skip-cpu > $O/c2_${v}_$i.json 2> $O/c2_${v}_$i.err || exit 1
+    timeout -k 10 300 python -u bench.py --full --workload c5 --precision medium --steps 30 --warmup 10 --skip-cpu > $O/c5m_${v}_$i.json 2> $O/c5m_${v}_$i.err || exit 1
+    timeout -k 10 300 python -u bench.py --full --workload c2 --steps 50 --warmup 10 --skip-cpu > $O/c2_${v}_$i.json 2> $O/c2_${v}_$i.err || exit 1
     echo "$v $i ok"
   done
 done
 for v in "$@"; do
   if [ $v = cur ]; then unset MMF_LIB_PATH; else export MMF_LIB_PATH=$GRAFT_REPO_ROOT/$C/libmmfusion_$v.so; fi
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$v -o run -- python -u bench.py --workload c5 --precision medium --steps 20 --warmup 5 --skip-cpu > $O/prof_$v.json 2> $O/prof_$v.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$v -o run -- python -u bench.py --full --workload c5 --precision medium --steps 20 --warmup 5 --skip-cpu > $O/prof_$v.json 2> $O/prof_$v.err || exit 1
   echo "prof $v ok"
 done
 echo done

@@ -14,8 +14,13 @@ GOLDEN = Path(__file__).resolve().parent / "golden"
 
 
 def load_fixture(name: str) -> Dict[str, np.ndarray]:
-    with np.load(GOLDEN / f"{name}.npz", allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    """<name>.npz, with the arrays of its <name>.part<N>.npz files (gen_golden.save_fixture keeps
+    every file under 1 MiB by moving the largest arrays into parts)."""
+    out = {}
+    for path in [GOLDEN / f"{name}.npz"] + sorted(GOLDEN.glob(f"{name}.part*.npz")):
+        with np.load(path, allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def _bf16(x: torch.Tensor) -> torch.Tensor:

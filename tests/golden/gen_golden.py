@@ -289,17 +289,46 @@ def gen_seqenc(ref_encoders, case):
     return out
 
 
+MAX_FILE_BYTES = 2 ** 20   # no committed file above 1 MiB
+
+
+def save_fixture(name, out):
+    """<name>.npz; while it is above MAX_FILE_BYTES its largest array moves into a file of its
+    own, <name>.part<N>.npz (tests/_util.load_fixture merges the parts back)."""
+    for old in HERE.glob(f"{name}.part*.npz"):
+        old.unlink()
+    main, parts = dict(out), 0
+    while True:
+        np.savez_compressed(HERE / f"{name}.npz", **main)
+        if (HERE / f"{name}.npz").stat().st_size <= MAX_FILE_BYTES:
+            break
+        parts += 1
+        key = max(main, key=lambda k: main[k].nbytes)
+        part = HERE / f"{name}.part{parts}.npz"
+        np.savez_compressed(part, **{key: main.pop(key)})
+        assert main and part.stat().st_size <= MAX_FILE_BYTES, f"{name}: {key} alone exceeds the file limit"
+    print(f"wrote {name}.npz ({sum(a.nbytes for a in out.values())} B raw" + (f", {parts} part file(s))" if parts else ")"))
+
+
+def gen_ref_init(ref_attention):
+    """The reference CrossModalAttention's own initial parameters under a seed
+    (tests/test_host_interface.py builds the package's module under the same seed)."""
+    torch.manual_seed(7)
+    model = ref_attention.CrossModalAttention(12, 20, hidden_dim=16, num_heads=4)
+    return {k: v.detach().numpy() for k, v in model.state_dict().items()}
+
+
 def main():
     only = set(sys.argv[1].split(",")) if len(sys.argv) > 1 else None   # e.g. seq_c2_b3,seq_lean_hd64
     torch.set_float32_matmul_precision("highest")
     torch.set_num_threads(4)
     ref_fusion, ref_attention, ref_encoders = _load_reference()
+    if not only or "ref_init_cma" in only:
+        save_fixture("ref_init_cma", gen_ref_init(ref_attention))
     for case in HYBRID_CASES:
         if only and case.name not in only:
             continue
-        out = gen_hybrid(ref_fusion, case)
-        np.savez_compressed(HERE / f"{case.name}.npz", **out)
-        print(f"wrote {case.name}.npz ({sum(a.nbytes for a in out.values())} B raw)")
+        save_fixture(case.name, gen_hybrid(ref_fusion, case))
     for cases, gen, mod in ((CMA_CASES, gen_cma, ref_attention), (TEMPORAL_CASES, gen_temporal, ref_attention),
                             (PAIRWISE_CASES, gen_pairwise, ref_attention),
                             (FRAMEPOOL_CASES, gen_framepool, ref_encoders), (LATE_CASES, gen_late, ref_fusion),
@@ -308,9 +337,7 @@ def main():
         for case in cases:
             if only and case.name not in only:
                 continue
-            out = gen(mod, case)
-            np.savez_compressed(HERE / f"{case.name}.npz", **out)
-            print(f"wrote {case.name}.npz ({sum(a.nbytes for a in out.values())} B raw)")
+            save_fixture(case.name, gen(mod, case))
 
 
 if __name__ == "__main__":

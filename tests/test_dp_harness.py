@@ -223,6 +223,34 @@ def test_bench_gpus_mismatch_refused(monkeypatch):
         bench.main(["--gpus", "4"])
 
 
+def test_bench_output_dump_budget_and_sample(tmp_path):
+    """--dump-outputs: arrays within the shared budget are written whole, a larger one as a fixed
+    sample of its own elements (the same indices on every call), float32, the total within the
+    budget; --dump-launches belongs to --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    g = torch.Generator().manual_seed(3)
+    outs = {"loss": torch.randn(1, generator=g), "logits": torch.randn(7, 5, generator=g),
+            "dx0": torch.randn(9, 11, 13, generator=g), "dx1": torch.randn(2000, generator=g).double()}
+    whole = bench.snapshot_outputs(outs)
+    assert all(whole[k].dtype == np.float32 and whole[k].shape == tuple(v.shape) for k, v in outs.items())
+    assert all(np.array_equal(whole[k], v.float().numpy()) for k, v in outs.items())
+    budget = 4 * (1 + 35 + 400 + 400)
+    a, b = bench.snapshot_outputs(outs, budget), bench.snapshot_outputs(outs, budget)
+    assert a["loss"].shape == (1,) and a["logits"].shape == (7, 5) and a["dx0"].shape == a["dx1"].shape == (400,)
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    for k in ("dx0", "dx1"):   # a sample of the array's own elements, spread over it
+        flat = outs[k].reshape(-1).float().numpy()
+        assert np.isin(a[k], flat).all() and len(np.unique(a[k])) > 300
+    bench.write_outputs(a, str(tmp_path / "d"))
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["dx0.npy", "dx1.npy", "logits.npy", "loss.npy"]
+    assert np.array_equal(np.load(tmp_path / "d" / "dx0.npy"), a["dx0"])
+    with pytest.raises(SystemExit, match="--full"):
+        bench.main(["--dump-launches", str(tmp_path / "l.json")])
+
+
 def test_model_from_base_config_keys():
     """MultimodalFusionModel.from_config builds config/base.yaml's PAMAP2 model (the keys of
     src/train.py:150-182): four LSTM SequenceEncoders, LayerNorms, HybridFusion H=256, h=4."""
