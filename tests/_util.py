@@ -211,3 +211,68 @@ def close(got, ref, rtol: float, atol: float = 0.0) -> bool:
     if ref.numel() == 0:
         return True
     return float((got - ref).abs().max()) <= rtol * float(ref.abs().max()) + atol
+
+
+EPS32 = 2.0 ** -24   # the unit roundoff of fp32: the floor of every measured oracle error below
+
+
+def _t64(x) -> torch.Tensor:
+    return torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).detach().double().cpu()
+
+
+def sliced_errors(got, ref64, ref32, slice_dim=0):
+    """Per slice along slice_dim (the sample index; None: the whole tensor is one slice):
+    (e_dev, e_32) = (max|got - ref64|, max|ref32 - ref64|), both divided by that slice's
+    max|ref64| -- or by the whole tensor's where the slice's float64 reference is identically
+    zero (a fully masked sample's gradients and attention rows).  Two 1-D float64 tensors."""
+    got, ref64, ref32 = _t64(got), _t64(ref64), _t64(ref32)
+    assert got.shape == ref64.shape == ref32.shape, (tuple(got.shape), tuple(ref64.shape), tuple(ref32.shape))
+    assert ref64.numel() > 0 and bool(torch.isfinite(ref64).all()) and bool(torch.isfinite(ref32).all())
+    if slice_dim is None or ref64.dim() == 0:
+        got, ref64, ref32 = (t.reshape(1, -1) for t in (got, ref64, ref32))
+    else:
+        got, ref64, ref32 = (t.movedim(slice_dim, 0).reshape(t.shape[slice_dim], -1) for t in (got, ref64, ref32))
+    whole = float(ref64.abs().max())
+    norm = ref64.abs().amax(dim=1)
+    norm = torch.where(norm > 0, norm, torch.full_like(norm, whole))
+    assert float(norm.min()) > 0, "the float64 reference is identically zero: nothing to normalise by"
+    e_dev = (got - ref64).abs().amax(dim=1) / norm
+    e_32 = (ref32 - ref64).abs().amax(dim=1) / norm
+    # a NaN anywhere must fail, not vanish in a max
+    e_dev = torch.where(torch.isfinite(got).all(dim=1), e_dev, torch.full_like(e_dev, float("inf")))
+    return e_dev, e_32
+
+
+def sliced_ratio(got, ref64, ref32, *, slice_dim=0):
+    """(largest e_dev / max(e_32, 2^-24) over the slices, largest e_dev): what close_sliced's c
+    and cap are compared with."""
+    e_dev, e_32 = sliced_errors(got, ref64, ref32, slice_dim)
+    return float((e_dev / e_32.clamp_min(EPS32)).max()), float(e_dev.max())
+
+
+def close_sliced(got, ref64, ref32, *, slice_dim=0, c, cap=1e-4) -> bool:
+    """Every slice along slice_dim has max|got - ref64| <= min(c * max(e_32, 2^-24), cap) of the
+    slice's max|ref64|, e_32 being the fp32 oracle's own distance from the float64 one in that
+    slice (sliced_errors): the device may be c times as far from float64 as plain fp32 CPU
+    arithmetic is, sample by sample, and never further than cap."""
+    e_dev, e_32 = sliced_errors(got, ref64, ref32, slice_dim)
+    bound = (c * e_32.clamp_min(EPS32)).clamp_max(cap)
+    return bool((e_dev <= bound).all())
+
+
+def sliced_report(got, ref64, ref32, *, slice_dim=0, c, cap=1e-4) -> str:
+    """For an assertion message: the slice furthest over (or nearest to) close_sliced's bound."""
+    e_dev, e_32 = sliced_errors(got, ref64, ref32, slice_dim)
+    bound = (c * e_32.clamp_min(EPS32)).clamp_max(cap)
+    i = int((e_dev / bound).argmax())
+    nbad = int((e_dev > bound).sum())
+    return (f"slice {i} of {e_dev.numel()}: e_dev {float(e_dev[i]):.3e}, e_32 {float(e_32[i]):.3e}, "
+            f"ratio {float(e_dev[i] / max(float(e_32[i]), EPS32)):.2f} (c = {c}), bound {float(bound[i]):.3e}, "
+            f"{nbad} slices over")
+
+
+def zero_grad_bound(ref32, scale: float, c: float) -> float:
+    """The absolute bound of a gradient that is mathematically zero (key_proj.bias: softmax is
+    shift invariant, the float64 oracle holds ~1e-16 there): c times the fp32 oracle's own
+    largest element there, floored at 2^-24 of the call's largest gradient."""
+    return max(c * float(_t64(ref32).abs().max()), EPS32 * scale)
