@@ -250,6 +250,61 @@ int mmf_late_fusion_backward(int32_t batch, int32_t num_modalities, int32_t num_
                              float* dweight_logits, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------
+ * Uncertainty quantification (src/uncertainty.py).  classes <= 1024 throughout
+ * (MMF_ELIMIT beyond); reductions run in a fixed order (bit-identical reruns).
+ *
+ * MC-dropout / ensemble reduction (src/uncertainty.py:58-66, :487-491) of a
+ * stack of logit samples logits_stack (S, B, C):
+ *   mean_logits (B, C) = mean_s z,  mean_probs (B, C) = mean_s softmax_c(z),
+ *   variance (B) = mean_c var_s(softmax_c(z)), the population variance
+ *   (unbiased=False), accumulated in Welford's shifted form (the samples of a
+ *   confident model differ in the 3rd-5th digit); exactly 0 for samples == 1.
+ * Each output may be NULL.  One launch (mc_reduce_kernel); the stack is read once.
+ * ------------------------------------------------------------------- */
+int mmf_mc_reduce(int32_t samples, int32_t batch, int32_t classes, const float* logits_stack,
+                  float* mean_logits, float* mean_probs, float* variance, void* stream);
+
+/* MCDropoutUncertainty.forward over HybridFusion (src/uncertainty.py:41-71) in one call: `samples`
+ * forwards of mmf_hybrid_forward's plan for this descriptor, sample s writing logits_stack[s]
+ * ((S, B, C)); `saved` (mmf_hybrid_saved_bytes, the buffer contract as in the forward) is reused by
+ * every sample and fusion_weights (B, M) holds the last sample's; then one mc_reduce_kernel launch
+ * into mean_logits / mean_probs / variance (each may be NULL).  Every forward advances the dropout
+ * offset by one on the device: the samples draw distinct masks and the offset ends advanced by
+ * exactly `samples`.  d->training must be 1 and d->return_attention 0, samples >= 1 (MMF_EINVAL).
+ * Profiling stages: "mc.forward", "mc.reduce". */
+int mmf_hybrid_mc_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* params,
+                          const float* const* x, const float* mask, uint64_t* rng_state,
+                          int32_t samples, void* saved, float* logits_stack, float* fusion_weights,
+                          float* mean_logits, float* mean_probs, float* variance, void* stream);
+
+/* TemperatureScaling.calibrate's closure (src/uncertainty.py:431-435) without an autograd graph:
+ * loss_out[0] = mean_i CE(z_i / T, y_i) and dtemp_out[0] = d loss / dT =
+ * mean_i (z_{i, y_i} - sum_c p_{i, c} z_{i, c}) / T^2 over logits (n, C), labels (n) int64, with
+ * T = temperature_dev[0] read on the device (no host round trip in an optimiser loop).  One pass
+ * over the logits; the per-workgroup partial sums in `workspace`
+ * (mmf_temperature_nll_workspace_bytes) are reduced by a second launch.  A label outside [0, C)
+ * makes both outputs NaN and is never used as an index.  Either output may be NULL. */
+size_t mmf_temperature_nll_workspace_bytes(int64_t n);
+int mmf_temperature_nll(int64_t n, int32_t classes, const float* logits, const int64_t* labels,
+                        const float* temperature_dev, float* loss_out, float* dtemp_out,
+                        void* workspace, void* stream);
+
+/* UncertaintyWeightedFusion.forward (src/uncertainty.py:305-362): logits (B, M, C) stacked
+ * per-modality predictions, uncertainty (B, M), mask (B, M).  w = mask / (uncertainty + epsilon);
+ * where a row's sum of w is > 0 the weights are w / (sum + 1e-8), otherwise mask / (sum mask +
+ * 1e-8), or 1 / M where the mask sums to 0.  Writes fused (B, C) = sum_m weights[b, m]
+ * logits[b, m, :] and weights (B, M).  M <= 64. */
+int mmf_uncertainty_fusion_forward(int32_t batch, int32_t num_modalities, int32_t num_classes,
+                                   const float* logits, const float* uncertainty, const float* mask,
+                                   float epsilon, float* fused, float* weights, void* stream);
+/* Backward of sum(fused * dfused): dlogits (B, M, C), duncertainty (B, M) (zero on fallback rows, as
+ * autograd through torch.where gives); either may be NULL. */
+int mmf_uncertainty_fusion_backward(int32_t batch, int32_t num_modalities, int32_t num_classes,
+                                    const float* logits, const float* uncertainty, const float* mask,
+                                    float epsilon, const float* dfused, float* dlogits,
+                                    float* duncertainty, void* stream);
+
+/* ---------------------------------------------------------------------
  * Manifest data path (src/data.py:110-343, MultimodalDataset over .pt shards
  * {columns, data (rows, ncols)}): gather a batch of chunk windows from the
  * HBM-resident shard table into per-modality tensors.

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "mmf_late_fusion_workspace_bytes", "mmf_late_fusion_forward", "mmf_late_fusion_backward",
     "mmf_gather_chunks",
     "mmf_lstm_sync_bytes", "mmf_lstm_forward", "mmf_lstm_backward",
+    "mmf_mc_reduce", "mmf_hybrid_mc_forward", "mmf_temperature_nll_workspace_bytes", "mmf_temperature_nll",
+    "mmf_uncertainty_fusion_forward", "mmf_uncertainty_fusion_backward",
 )
 
 
@@ -215,6 +217,19 @@ def lib() -> ctypes.CDLL:
     L.mmf_lstm_forward.restype = c_int32
     L.mmf_lstm_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mmf_lstm_backward.restype = c_int32
+    L.mmf_mc_reduce.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, vp, vp]
+    L.mmf_mc_reduce.restype = c_int32
+    L.mmf_hybrid_mc_forward.argtypes = [POINTER(HybridDesc), POINTER(HybridParams), vp, vp, vp, c_int32, vp, vp, vp,
+                                        vp, vp, vp, vp]
+    L.mmf_hybrid_mc_forward.restype = c_int32
+    L.mmf_temperature_nll_workspace_bytes.argtypes = [c_int64]
+    L.mmf_temperature_nll_workspace_bytes.restype = sz
+    L.mmf_temperature_nll.argtypes = [c_int64, c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.mmf_temperature_nll.restype = c_int32
+    L.mmf_uncertainty_fusion_forward.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, c_float, vp, vp, vp]
+    L.mmf_uncertainty_fusion_forward.restype = c_int32
+    L.mmf_uncertainty_fusion_backward.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, c_float, vp, vp, vp, vp]
+    L.mmf_uncertainty_fusion_backward.restype = c_int32
     L.mmf_last_error.argtypes = []
     L.mmf_last_error.restype = ctypes.c_char_p
     L.mmf_version.argtypes = []

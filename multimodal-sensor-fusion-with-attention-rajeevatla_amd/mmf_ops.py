@@ -24,6 +24,9 @@ Operators (csrc entry point, reference interface):
   attention_pool_fwd / _bwd        mmf_attention_pool_*              src/encoders.py:313-336
   late_weights_fwd / _bwd          mmf_late_fusion_*                 src/fusion.py:228-245
   lstm_layer_fwd / _bwd            mmf_lstm_forward / _backward      src/encoders.py:135-166
+  mc_reduce                        mmf_mc_reduce                     src/uncertainty.py:58-66, 487-491
+  temperature_nll                  mmf_temperature_nll               src/uncertainty.py:431-435
+  uncertainty_fusion_fwd / _bwd    mmf_uncertainty_fusion_*          src/uncertainty.py:305-362
 """
 
 from __future__ import annotations
@@ -913,3 +916,117 @@ def cross_entropy(logits: Tensor, labels: Tensor, label_smoothing: float = 0.0, 
             return ext.cross_entropy(logits.contiguous(), labels.contiguous(), float(label_smoothing))
         return CrossEntropyEager.apply(logits.contiguous(), labels.contiguous(), float(label_smoothing))
     return torch.ops.mmfusion.cross_entropy_ls_fwd(logits.contiguous(), labels.contiguous(), float(label_smoothing))[0]
+
+
+# ============================================================================ Uncertainty (src/uncertainty.py)
+@torch.library.custom_op("mmfusion::mc_reduce", mutates_args=(), device_types="cuda")
+def mc_reduce(stack: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """(S, B, C) logit samples -> mean logits (B, C), mean softmax (B, C), mean_c var_s softmax (B,)
+    (population variance, Welford form) in one launch of mc_reduce_kernel: the reduction of
+    MCDropoutUncertainty.forward / EnsembleUncertainty.predict_with_uncertainty
+    (src/uncertainty.py:58-66, 487-491).  Not differentiable (the reference runs it under no_grad)."""
+    L = _nat.lib()
+    S, B, C = stack.shape
+    dev = stack.device
+    mean_logits = torch.empty(B, C, dtype=torch.float32, device=dev)
+    mean_probs = torch.empty(B, C, dtype=torch.float32, device=dev)
+    variance = torch.empty(B, dtype=torch.float32, device=dev)
+    rc = L.mmf_mc_reduce(S, B, C, stack.data_ptr(), mean_logits.data_ptr(), mean_probs.data_ptr(),
+                         variance.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "MC reduce")
+    return mean_logits, mean_probs, variance
+
+
+@mc_reduce.register_fake
+def _(stack):
+    S, B, C = stack.shape
+    return stack.new_empty(B, C), stack.new_empty(B, C), stack.new_empty(B)
+
+
+@torch.library.custom_op("mmfusion::temperature_nll", mutates_args=(), device_types="cuda")
+def temperature_nll(logits: Tensor, labels: Tensor, temperature: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (mean cross-entropy of logits / T, d loss / dT), T = temperature[0] read on the device
+    (mmf_temperature_nll: TemperatureScaling.calibrate's closure, src/uncertainty.py:431-435)."""
+    L = _nat.lib()
+    N, C = logits.shape
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dtemp = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = torch.empty(L.mmf_temperature_nll_workspace_bytes(N), dtype=torch.uint8, device=dev)
+    rc = L.mmf_temperature_nll(N, C, logits.data_ptr(), labels.data_ptr(), temperature.data_ptr(), loss.data_ptr(),
+                               dtemp.data_ptr(), ws.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "temperature NLL")
+    return loss, dtemp
+
+
+@temperature_nll.register_fake
+def _(logits, labels, temperature):
+    return logits.new_empty(()), logits.new_empty(1)
+
+
+def _tn_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _tn_backward(ctx, dloss, _ddtemp):
+    (dtemp,) = ctx.saved_tensors
+    return None, None, dtemp * dloss
+
+
+temperature_nll.register_autograd(_tn_backward, setup_context=_tn_setup)
+
+
+@torch.library.custom_op("mmfusion::uncertainty_fusion_fwd", mutates_args=(), device_types="cuda")
+def uncertainty_fusion_fwd(stacked: Tensor, uncertainty: Tensor, mask: Tensor, epsilon: float) -> Tuple[Tensor, Tensor]:
+    """UncertaintyWeightedFusion (src/uncertainty.py:305-362) -> fused (B, C), weights (B, M)."""
+    L = _nat.lib()
+    B, M, C = stacked.shape
+    dev = stacked.device
+    fused = torch.empty(B, C, dtype=torch.float32, device=dev)
+    weights = torch.empty(B, M, dtype=torch.float32, device=dev)
+    rc = L.mmf_uncertainty_fusion_forward(B, M, C, stacked.data_ptr(), uncertainty.data_ptr(), mask.data_ptr(),
+                                          float(epsilon), fused.data_ptr(), weights.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "UncertaintyWeightedFusion forward")
+    return fused, weights
+
+
+@uncertainty_fusion_fwd.register_fake
+def _(stacked, uncertainty, mask, epsilon):
+    B, M, C = stacked.shape
+    return stacked.new_empty(B, C), stacked.new_empty(B, M)
+
+
+@torch.library.custom_op("mmfusion::uncertainty_fusion_bwd", mutates_args=(), device_types="cuda")
+def uncertainty_fusion_bwd(stacked: Tensor, uncertainty: Tensor, mask: Tensor, epsilon: float,
+                           dfused: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> d stacked (B, M, C), d uncertainty (B, M) (zero on the fallback rows)."""
+    L = _nat.lib()
+    B, M, C = stacked.shape
+    dev = stacked.device
+    dstacked = torch.empty_like(stacked)
+    du = torch.empty(B, M, dtype=torch.float32, device=dev)
+    rc = L.mmf_uncertainty_fusion_backward(B, M, C, stacked.data_ptr(), uncertainty.data_ptr(), mask.data_ptr(),
+                                           float(epsilon), dfused.data_ptr(), dstacked.data_ptr(), du.data_ptr(),
+                                           _nat.stream_ptr(dev))
+    _nat.check(rc, "UncertaintyWeightedFusion backward")
+    return dstacked, du
+
+
+@uncertainty_fusion_bwd.register_fake
+def _(stacked, uncertainty, mask, epsilon, dfused):
+    return torch.empty_like(stacked), stacked.new_empty(stacked.size(0), stacked.size(1))
+
+
+def _uf_setup(ctx, inputs, output):
+    stacked, uncertainty, mask, epsilon = inputs
+    ctx.save_for_backward(stacked, uncertainty, mask)
+    ctx.epsilon = epsilon
+
+
+def _uf_backward(ctx, dfused, _dweights):
+    stacked, uncertainty, mask = ctx.saved_tensors
+    ds, du = torch.ops.mmfusion.uncertainty_fusion_bwd(stacked, uncertainty, mask, ctx.epsilon, dfused.contiguous())
+    return ds, du, None, None
+
+
+uncertainty_fusion_fwd.register_autograd(_uf_backward, setup_context=_uf_setup)
