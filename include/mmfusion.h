@@ -356,6 +356,43 @@ int mmf_lstm_backward(int32_t num_lstm, int32_t batch, int32_t steps, int32_t hi
                       void* stream);
 
 /* ---------------------------------------------------------------------
+ * CNN sequence encoder's conv stack (SequenceEncoder 'cnn', src/encoders.py:87-97 / 168-175):
+ *   Conv1d(in_dim, hidden, 3, padding=1) -> BatchNorm1d -> ReLU ->
+ *   Conv1d(hidden, hidden, 3, padding=1) -> BatchNorm1d -> ReLU -> mean over the steps.
+ * Layouts (all fp32, contiguous): activations channels-last, x (B, T, in_dim), y1 / y2 (B, T,
+ * hidden) the two conv outputs (before BatchNorm; written by the forward, read by the backward);
+ * conv weights REPACKED as (out, 3, in) -- torch's (out, in, 3) permuted (0, 2, 1) -- with their
+ * gradients in the same layout; biases, gamma / beta, running mean / var (hidden).  Rows outside
+ * 0 <= t < T are zero padding, applied after BatchNorm-1 + ReLU for the second conv.
+ * training != 0: BatchNorm uses the batch statistics over B * T (biased variance, computed from
+ * centred values); == 0: the running statistics.  stat1 / stat2 (6, hidden) are written by the
+ * forward: rows = mean, biased variance, 1 / sqrt(var + eps), gamma / sqrt(var + eps), beta, and
+ * the part of the batch mean fp32 cannot hold (mean - row 0; 0 in eval), of the statistics used
+ * (the caller updates its running buffers from rows 0 and 1) and read by the backward.  pooled (B, hidden).  Backward of sum(pooled * dpooled): every parameter gradient is
+ * WRITTEN (dgamma / dbeta are BatchNorm's weight / bias gradients); dx (B, T, in_dim) may be NULL
+ * (not computed).  Reductions run in a fixed order with kernel boundaries between their phases (no
+ * atomics, no inter-workgroup waits): reruns are bit-identical.  The matmuls are fp32 MFMA at
+ * every matmul-precision setting.
+ * Limits: hidden a multiple of 32 up to 512, in_dim 1..4096, 1 <= B * T <= 2^24 (MMF_ELIMIT;
+ * B * T == 0 is MMF_EINVAL), checked before anything touches the device.
+ * workspace: mmf_conv_encoder_workspace_bytes(..., backward = 0 / 1) bytes (0 with an error message
+ * for a shape outside the limits).
+ * ------------------------------------------------------------------- */
+size_t mmf_conv_encoder_workspace_bytes(int32_t batch, int32_t steps, int32_t in_dim, int32_t hidden,
+                                        int32_t backward);
+int mmf_conv_encoder_forward(int32_t batch, int32_t steps, int32_t in_dim, int32_t hidden, int32_t training,
+                             const float* x, const float* w1, const float* b1, const float* gamma1,
+                             const float* beta1, const float* rmean1, const float* rvar1, float eps1,
+                             const float* w2, const float* b2, const float* gamma2, const float* beta2,
+                             const float* rmean2, const float* rvar2, float eps2, float* y1, float* y2,
+                             float* stat1, float* stat2, float* pooled, void* workspace, void* stream);
+int mmf_conv_encoder_backward(int32_t batch, int32_t steps, int32_t in_dim, int32_t hidden, int32_t training,
+                              const float* x, const float* w1, const float* w2, const float* y1, const float* y2,
+                              const float* stat1, const float* stat2, const float* dpooled, float* dx, float* dw1,
+                              float* db1, float* dgamma1, float* dbeta1, float* dw2, float* db2, float* dgamma2,
+                              float* dbeta2, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------
  * Training-step helpers used by the data-parallel step (not part of the
  * reference interface; the reference uses torch.optim.AdamW via Lightning,
  * src/train.py:374-414).

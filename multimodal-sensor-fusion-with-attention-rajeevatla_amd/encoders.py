@@ -27,8 +27,21 @@ time-parallel input projection and weight gradients are rocBLAS GEMMs.
 launches.  The recurrence's workgroups wait on each other: the library refuses
 a grid that cannot be co-resident, every launch gets a fresh timeout word, and
 a wait that gives up poisons its outputs with NaN; ``lstm_timed_out()`` /
-``check_lstm_timeouts()`` report such launches (one stream sync per check).  The 'gru' / 'cnn' / 'transformer' encoder types are not on the
+``check_lstm_timeouts()`` report such launches (one stream sync per check).  The 'gru' / 'transformer' encoder types are not on the
 path and raise NotImplementedError.
+
+ConvSequenceEncoder mirrors the reference's 'cnn' branch (src/encoders.py:87-97, 168-175:
+Conv1d(k=3, pad=1) -> BatchNorm1d -> ReLU, twice, -> AdaptiveAvgPool1d(1) -> dropout -> Linear),
+with the reference's state_dict keys (conv_net.{0,1,3,4}.*, projection.*) and initialisation.
+``conv_net`` holds the parameters and buffers; the conv stack up to the pooled (B, hidden)
+vector runs forward and backward as the HIP kernels behind mmf_conv_encoder_forward / _backward
+(csrc/conv_encoder.hip: channels-last implicit GEMMs on the fp32 matrix cores, BatchNorm-1
+applied while conv 2's input tile is staged, batch statistics from centred values, fixed-order
+reductions, no inter-workgroup waits).  The matmuls are fp32 MFMA at every
+torch.get_float32_matmul_precision() setting (more precise than "high" / "medium" ask for).
+SequenceEncoder(..., encoder_type="cnn") itself still raises NotImplementedError, naming
+ConvSequenceEncoder; ``build_encoder`` (the reference's factory, src/encoders.py:400-451) returns
+the right class for a modality and its config.
 """
 
 from __future__ import annotations
@@ -304,8 +317,12 @@ class SequenceEncoder(nn.Module):
             cast_self.rnn = LSTM(input_dim, hidden_dim, num_layers=num_layers, batch_first=True,
                                  dropout=dropout if num_layers > 1 else 0.0)
             self.projection = nn.Linear(hidden_dim, output_dim)
-        elif encoder_type in ("gru", "cnn", "transformer"):
-            raise NotImplementedError(f"encoder_type '{encoder_type}' is not on the MI355X path (only 'lstm')")
+        elif encoder_type == "cnn":
+            raise NotImplementedError("encoder_type 'cnn' is served by ConvSequenceEncoder (build_encoder returns it "
+                                      "for encoder_type='cnn'), not by SequenceEncoder")
+        elif encoder_type in ("gru", "transformer"):
+            raise NotImplementedError(f"encoder_type '{encoder_type}' is not on the MI355X path (only 'lstm', and "
+                                      "'cnn' through ConvSequenceEncoder / build_encoder)")
         else:
             raise ValueError(f"Unknown encoder type: {encoder_type}")
 
@@ -319,6 +336,122 @@ class SequenceEncoder(nn.Module):
             raise RuntimeError("RNN module not initialized.")
         out = lstm_layers([self.rnn], [sequence])[0]
         return self.encode_final_state(_final_state(out, lengths))
+
+
+class ConvSequenceEncoder(nn.Module):
+    """The reference SequenceEncoder's 'cnn' branch (src/encoders.py:87-97, 168-175) on the HIP path:
+    the same attributes, construction order (the same seed gives the same weights) and state_dict.
+    ``conv_net`` is the reference's nn.Sequential and only holds the parameters and buffers; the
+    stack runs in csrc/conv_encoder.hip.  ``num_layers`` is accepted and ignored, as there."""
+
+    encoder_type: str
+    hidden_dim: int
+    output_dim: int
+    rnn: Optional[nn.Module]
+    conv_net: Optional[nn.Module]
+    pool: Optional[nn.Module]
+    input_projection: Optional[nn.Linear]
+    transformer: Optional[nn.TransformerEncoder]
+    projection: nn.Module
+
+    def __init__(self, input_dim: int, hidden_dim: int = 256, output_dim: int = 128, num_layers: int = 2,
+                 dropout: float = 0.1):
+        super().__init__()
+        cast_self = cast(Any, self)
+        cast_self.encoder_type = "cnn"
+        cast_self.hidden_dim = hidden_dim
+        cast_self.output_dim = output_dim
+        self.dropout_layer = nn.Dropout(dropout)
+        cast_self.rnn = None
+        cast_self.input_projection = None
+        cast_self.transformer = None
+        cast_self.conv_net = nn.Sequential(
+            nn.Conv1d(input_dim, hidden_dim, kernel_size=3, padding=1), nn.BatchNorm1d(hidden_dim), nn.ReLU(),
+            nn.Conv1d(hidden_dim, hidden_dim, kernel_size=3, padding=1), nn.BatchNorm1d(hidden_dim), nn.ReLU())
+        cast_self.pool = nn.AdaptiveAvgPool1d(1)
+        self.projection = nn.Linear(hidden_dim, output_dim)
+
+    def _stack(self):
+        """(conv1, bn1, conv2, bn2) when conv_net is still the structure the kernels implement."""
+        net = self.conv_net
+        mods = list(net.children()) if isinstance(net, nn.Sequential) else []
+        kinds = (nn.Conv1d, nn.BatchNorm1d, nn.ReLU, nn.Conv1d, nn.BatchNorm1d, nn.ReLU)
+        ok = len(mods) == 6 and all(isinstance(m, k) for m, k in zip(mods, kinds))
+        if ok:
+            c1, b1, _, c2, b2, _ = mods
+            for c in (c1, c2):
+                ok = ok and (c.kernel_size, c.stride, c.padding, c.dilation, c.groups) == ((3,), (1,), (1,), (1,), 1)
+                ok = ok and c.padding_mode == "zeros" and c.bias is not None
+            for b in (b1, b2):
+                ok = ok and b.affine and b.track_running_stats and b.running_mean is not None
+            ok = ok and c1.out_channels == c2.in_channels == c2.out_channels == b1.num_features == b2.num_features
+            ok = ok and b1.training == b2.training
+            ok = ok and isinstance(self.pool, nn.AdaptiveAvgPool1d) and self.pool.output_size in (1, (1,))
+        if not ok:
+            raise NotImplementedError("ConvSequenceEncoder: the HIP path implements Conv1d(k=3, padding=1) -> "
+                                      "BatchNorm1d -> ReLU, twice, -> AdaptiveAvgPool1d(1) only (there is no torch "
+                                      "fallback)")
+        return c1, b1, c2, b2
+
+    @staticmethod
+    def _track(bn: nn.BatchNorm1d, stat: torch.Tensor, n: int) -> None:
+        """torch's running-statistics rule from the batch statistics the kernel returned (mean, biased
+        variance): a few tiny device ops, no host sync."""
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+            if bn.momentum is None:
+                f = 1.0 / bn.num_batches_tracked.to(torch.float32)   # cumulative moving average
+            else:
+                f = float(bn.momentum)
+            mean, var = stat[0], stat[1] * (n / (n - 1))
+            bn.running_mean.mul_(1.0 - f).add_(mean * f)
+            bn.running_var.mul_(1.0 - f).add_(var * f)
+
+    def forward(self, sequence: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if sequence.dim() != 3:
+            raise ValueError(f"Expected 3D input sequence, got shape {sequence.shape}")
+        if self.conv_net is None or self.pool is None:
+            raise RuntimeError("CNN modules not initialized.")
+        c1, b1, c2, b2 = self._stack()
+        _nat.require_device(sequence, "ConvSequenceEncoder input")
+        x = _nat.f32c(sequence)
+        B, T, _ = x.shape
+        training = bool(b1.training)
+        if training and B * T <= 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             f"{torch.Size([B, c1.out_channels, T])}")
+        # (Cout, Cin, 3) -> (Cout, 3, Cin): autograd permutes the gradient back to torch's layout
+        w1 = c1.weight.permute(0, 2, 1).contiguous()
+        w2 = c2.weight.permute(0, 2, 1).contiguous()
+        pooled, _y1, _y2, stat1, stat2 = torch.ops.mmfusion.conv_encoder_fwd(
+            x, w1, c1.bias, b1.weight, b1.bias, b1.running_mean, b1.running_var,
+            w2, c2.bias, b2.weight, b2.bias, b2.running_mean, b2.running_var, training, float(b1.eps), float(b2.eps))
+        if training:
+            self._track(b1, stat1.detach(), B * T)
+            self._track(b2, stat2.detach(), B * T)
+        return self.projection(self.dropout_layer(pooled))
+
+
+def build_encoder(modality: str, input_dim: int, output_dim: int,
+                  encoder_config: Optional[Dict[str, Any]] = None) -> nn.Module:
+    """The reference's factory (src/encoders.py:400-451): the config's ``type`` ('frame' /
+    'sequence' / 'mlp') decides, else the modality name (video / frames -> FrameEncoder; imu /
+    audio / mocap / accelerometer / imu_* -> sequence).  A sequence encoder with
+    ``encoder_type == 'cnn'`` is a ConvSequenceEncoder, any other a SequenceEncoder.  The MLP
+    encoder (type 'mlp' and unknown modalities) is not on the MI355X path."""
+    config: Dict[str, Any] = dict(encoder_config) if encoder_config else {}
+    kind = config.pop("type", None)
+    key = modality.lower()
+    by_name = kind not in ("frame", "sequence", "mlp")
+    if kind == "frame" or (by_name and key in ("video", "frames")):
+        return FrameEncoder(frame_dim=input_dim, output_dim=output_dim, **config)
+    if kind == "sequence" or (by_name and (key in ("imu", "audio", "mocap", "accelerometer") or key.startswith("imu_"))):
+        if config.get("encoder_type", "lstm") == "cnn":
+            config.pop("encoder_type")
+            return ConvSequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
+        return SequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
+    # SimpleMLPEncoder (src/encoders.py:339-397) serves config 1's EarlyFusion CPU plumbing only
+    raise NotImplementedError(f"encoder for modality '{modality}' ({kind or 'mlp'}) is not on the MI355X path")
 
 
 def encode_sequences(encoders: Dict[str, SequenceEncoder], sequences: Dict[str, torch.Tensor],

@@ -91,7 +91,7 @@ class MultimodalFusionModel(nn.Module):
         """Build from config/base.yaml's keys: dataset.modalities, dataset.num_classes,
         model.{encoders, output_dim, hidden_dim, num_heads, dropout, fusion_type, layer_norm}
         (the construction order of src/train.py:150-182)."""
-        from encoders import FrameEncoder, SequenceEncoder
+        from encoders import build_encoder
         from fusion import build_fusion_model
         ds, mc = config["dataset"], config["model"]
         out_dim = int(mc["output_dim"])
@@ -99,16 +99,9 @@ class MultimodalFusionModel(nn.Module):
         for m in ds["modalities"]:
             ec = dict(mc.get("encoders", {}).get(m, {}))
             in_dim = int(ec.pop("input_dim", 64))
-            kind = ec.pop("type", None)
-            key = m.lower()
-            if kind == "frame" or (kind is None and key in ("video", "frames")):
-                encs[m] = FrameEncoder(frame_dim=in_dim, output_dim=out_dim, **ec)
-            elif kind == "sequence" or (kind is None and (key in ("imu", "audio", "mocap", "accelerometer")
-                                                          or key.startswith("imu_"))):
-                encs[m] = SequenceEncoder(input_dim=in_dim, output_dim=out_dim, **ec)
-            else:
-                # SimpleMLPEncoder (src/encoders.py:339-397) serves config 1's EarlyFusion CPU plumbing only
-                raise NotImplementedError(f"encoder for modality '{m}' ({kind or 'mlp'}) is not on the MI355X path")
+            # FrameEncoder / SequenceEncoder ('lstm') / ConvSequenceEncoder ('cnn'); the MLP encoder and
+            # unknown modalities raise NotImplementedError
+            encs[m] = build_encoder(m, in_dim, out_dim, ec)
         fusion = build_fusion_model(mc.get("fusion_type", "hybrid"), {m: out_dim for m in encs},
                                     int(ds.get("num_classes", 11)), hidden_dim=int(mc["hidden_dim"]),
                                     num_heads=int(mc.get("num_heads", 4)), dropout=float(mc["dropout"]))

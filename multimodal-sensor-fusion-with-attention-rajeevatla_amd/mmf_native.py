@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "mmf_lstm_sync_bytes", "mmf_lstm_forward", "mmf_lstm_backward",
     "mmf_mc_reduce", "mmf_hybrid_mc_forward", "mmf_temperature_nll_workspace_bytes", "mmf_temperature_nll",
     "mmf_uncertainty_fusion_forward", "mmf_uncertainty_fusion_backward",
+    "mmf_conv_encoder_workspace_bytes", "mmf_conv_encoder_forward", "mmf_conv_encoder_backward",
 )
 
 
@@ -230,6 +231,13 @@ def lib() -> ctypes.CDLL:
     L.mmf_uncertainty_fusion_forward.restype = c_int32
     L.mmf_uncertainty_fusion_backward.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, c_float, vp, vp, vp, vp]
     L.mmf_uncertainty_fusion_backward.restype = c_int32
+    L.mmf_conv_encoder_workspace_bytes.argtypes = [c_int32] * 5
+    L.mmf_conv_encoder_workspace_bytes.restype = sz
+    L.mmf_conv_encoder_forward.argtypes = ([c_int32] * 5 + [vp] * 7 + [c_float] + [vp] * 6 + [c_float]
+                                           + [vp] * 7)
+    L.mmf_conv_encoder_forward.restype = c_int32
+    L.mmf_conv_encoder_backward.argtypes = [c_int32] * 5 + [vp] * 19
+    L.mmf_conv_encoder_backward.restype = c_int32
     L.mmf_last_error.argtypes = []
     L.mmf_last_error.restype = ctypes.c_char_p
     L.mmf_version.argtypes = []

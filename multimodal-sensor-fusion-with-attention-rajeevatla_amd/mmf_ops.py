@@ -27,6 +27,7 @@ Operators (csrc entry point, reference interface):
   mc_reduce                        mmf_mc_reduce                     src/uncertainty.py:58-66, 487-491
   temperature_nll                  mmf_temperature_nll               src/uncertainty.py:431-435
   uncertainty_fusion_fwd / _bwd    mmf_uncertainty_fusion_*          src/uncertainty.py:305-362
+  conv_encoder_fwd / _bwd          mmf_conv_encoder_forward / _backward  src/encoders.py:87-97, 168-175
 """
 
 from __future__ import annotations
@@ -1030,3 +1031,92 @@ def _uf_backward(ctx, dfused, _dweights):
 
 
 uncertainty_fusion_fwd.register_autograd(_uf_backward, setup_context=_uf_setup)
+
+
+# ============================================================================ CNN sequence encoder (conv stack)
+@torch.library.custom_op("mmfusion::conv_encoder_fwd", mutates_args=(), device_types="cuda")
+def conv_encoder_fwd(x: Tensor, w1: Tensor, b1: Tensor, g1: Tensor, be1: Tensor, rm1: Tensor, rv1: Tensor,
+                     w2: Tensor, b2: Tensor, g2: Tensor, be2: Tensor, rm2: Tensor, rv2: Tensor, training: bool,
+                     eps1: float, eps2: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Conv1d(3, pad 1) -> BatchNorm1d -> ReLU, twice, -> mean over T (src/encoders.py:87-97, 168-175) on
+    x (B, T, Cin) channels-last; w1 (H, 3, Cin) / w2 (H, 3, H) are the conv weights permuted (0, 2, 1).
+    -> pooled (B, H), the conv outputs y1, y2 (B, T, H) and the BatchNorm statistics used stat1, stat2
+    (6, H) = mean, biased var, rstd, gamma * rstd, beta, mean_lo (the batch's when training, else the running ones)."""
+    L = _nat.lib()
+    B, T, Cin = x.shape
+    H = w1.size(0)
+    dev = x.device
+    pooled = torch.empty(B, H, dtype=torch.float32, device=dev)
+    y1 = torch.empty(B, T, H, dtype=torch.float32, device=dev)
+    y2 = torch.empty(B, T, H, dtype=torch.float32, device=dev)
+    stat1 = torch.empty(6, H, dtype=torch.float32, device=dev)
+    stat2 = torch.empty(6, H, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(256, L.mmf_conv_encoder_workspace_bytes(B, T, Cin, H, 0)), dtype=torch.uint8, device=dev)
+    rc = L.mmf_conv_encoder_forward(B, T, Cin, H, int(training), x.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                                    g1.data_ptr(), be1.data_ptr(), rm1.data_ptr(), rv1.data_ptr(), float(eps1),
+                                    w2.data_ptr(), b2.data_ptr(), g2.data_ptr(), be2.data_ptr(), rm2.data_ptr(),
+                                    rv2.data_ptr(), float(eps2), y1.data_ptr(), y2.data_ptr(), stat1.data_ptr(),
+                                    stat2.data_ptr(), pooled.data_ptr(), ws.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "ConvSequenceEncoder forward")
+    return pooled, y1, y2, stat1, stat2
+
+
+@conv_encoder_fwd.register_fake
+def _(x, w1, b1, g1, be1, rm1, rv1, w2, b2, g2, be2, rm2, rv2, training, eps1, eps2):
+    B, T, _ = x.shape
+    H = w1.size(0)
+    return x.new_empty(B, H), x.new_empty(B, T, H), x.new_empty(B, T, H), x.new_empty(6, H), x.new_empty(6, H)
+
+
+@torch.library.custom_op("mmfusion::conv_encoder_bwd", mutates_args=(), device_types="cuda")
+def conv_encoder_bwd(x: Tensor, w1: Tensor, w2: Tensor, y1: Tensor, y2: Tensor, stat1: Tensor, stat2: Tensor,
+                     dpooled: Tensor, training: bool, need_dx: bool) -> List[Tensor]:
+    """-> [dx (empty unless need_dx), dw1, db1, dgamma1, dbeta1, dw2, db2, dgamma2, dbeta2]; the weight
+    gradients in the (H, 3, Cin) layout of w1 / w2."""
+    L = _nat.lib()
+    B, T, Cin = x.shape
+    H = w1.size(0)
+    dev = x.device
+    dx = torch.empty_like(x) if need_dx else x.new_empty(0)
+    dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+    vecs = [torch.empty(H, dtype=torch.float32, device=dev) for _ in range(6)]
+    db1, dg1, dbe1, db2, dg2, dbe2 = vecs
+    ws = torch.empty(max(256, L.mmf_conv_encoder_workspace_bytes(B, T, Cin, H, 1)), dtype=torch.uint8, device=dev)
+    rc = L.mmf_conv_encoder_backward(B, T, Cin, H, int(training), x.data_ptr(), w1.data_ptr(), w2.data_ptr(),
+                                     y1.data_ptr(), y2.data_ptr(), stat1.data_ptr(), stat2.data_ptr(),
+                                     dpooled.data_ptr(), dx.data_ptr() if need_dx else None, dw1.data_ptr(),
+                                     db1.data_ptr(), dg1.data_ptr(), dbe1.data_ptr(), dw2.data_ptr(), db2.data_ptr(),
+                                     dg2.data_ptr(), dbe2.data_ptr(), ws.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "ConvSequenceEncoder backward")
+    return [dx, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2]
+
+
+@conv_encoder_bwd.register_fake
+def _(x, w1, w2, y1, y2, stat1, stat2, dpooled, training, need_dx):
+    H = w1.size(0)
+    v = [x.new_empty(H) for _ in range(6)]
+    return [torch.empty_like(x) if need_dx else x.new_empty(0), torch.empty_like(w1), v[0], v[1], v[2],
+            torch.empty_like(w2), v[3], v[4], v[5]]
+
+
+def _ce_conv_setup(ctx, inputs, output):
+    x, w1, _b1, _g1, _be1, _rm1, _rv1, w2 = inputs[:8]
+    _pooled, y1, y2, stat1, stat2 = output
+    # the saved activations and statistics reach the backward as None, not as materialised zeros
+    ctx.set_materialize_grads(False)
+    ctx.training = bool(inputs[13])
+    ctx.need_dx = bool(x.requires_grad)
+    ctx.save_for_backward(x, w1, w2, y1, y2, stat1, stat2)
+
+
+def _ce_conv_backward(ctx, dpooled, _dy1, _dy2, _ds1, _ds2):
+    if dpooled is None:
+        return (None,) * 16
+    x, w1, w2, y1, y2, stat1, stat2 = ctx.saved_tensors
+    dx, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2 = torch.ops.mmfusion.conv_encoder_bwd(
+        x, w1, w2, y1, y2, stat1, stat2, dpooled.contiguous(), ctx.training, ctx.need_dx)
+    return (dx if ctx.need_dx else None, dw1, db1, dg1, dbe1, None, None, dw2, db2, dg2, dbe2, None, None,
+            None, None, None)
+
+
+conv_encoder_fwd.register_autograd(_ce_conv_backward, setup_context=_ce_conv_setup)
