@@ -356,6 +356,44 @@ int mmf_lstm_backward(int32_t num_lstm, int32_t batch, int32_t steps, int32_t hi
                       void* stream);
 
 /* ---------------------------------------------------------------------
+ * GRU recurrence (SequenceEncoder's nn.GRU, src/encoders.py:77-85 / 135-166;
+ * torch.nn.GRU semantics, gate order r, z, n, zero initial state), on the
+ * LSTM's plan and exchange: one persistent launch runs all `steps` time steps
+ * of up to 8 independent GRUs; each GRU's batch is split into instances of
+ * <= 4 rows (G = hidden / 64 workgroups of 1024 threads each, all co-resident).
+ * The caller computes the time-parallel part,
+ *   xproj = x W_ih^T + b_ih + [b_hr, b_hz, 0]   (B, T, 3H),
+ * and the kernel runs, with h_{-1} = 0,
+ *   a = W_hh h_{t-1};  r = sigmoid(xproj_r + a_r);  z = sigmoid(xproj_z + a_z);
+ *   q = a_n + b_hn;  n = tanh(xproj_n + r q);  h_t = (1 - z) n + z h_{t-1}
+ * (b_hn is multiplied by r, so it cannot be folded into xproj).  All fp32 FMA
+ * at every matmul-precision setting.
+ * Limits: hidden a multiple of 64 up to 256, num_gru <= 8,
+ * num_gru * ceil(batch / 4) <= 32 (MMF_ELIMIT before anything touches the
+ * device); a NULL timeout or a w_hh that is not 16-byte aligned: MMF_EINVAL.
+ * Arrays are HOST arrays of num_gru device pointers:
+ *   xproj (B, T, 3H), w_hh (3H, H), b_hn (H), h (B, T, H), gates (B, T, 4H) =
+ *   (r, z, n, q) saved for the backward;
+ *   dh (B, T, H) upstream gradient of every h_t (entries may be NULL = 0),
+ *   dgates (B, T, 4H) = (dr_pre, dz_pre, dn_pre, dn_pre * r): d xproj is its
+ *   first 3H columns; with dgh = columns [0, 2H) and [3H, 4H),
+ *   dW_hh = sum_{t > 0} dgh_t^T h_{t-1} and db_hn = sum_{b, t} dgh[..., 2H:].
+ * sync[i]: device scratch of mmf_gru_sync_bytes(batch, hidden) bytes per GRU
+ * (the LSTM's formula; re-zeroed on the stream by every call).  timeout: as
+ * for the LSTM: zeroed by every call, ORed with 1 if an inter-workgroup wait
+ * gives up, and the values that never arrived are NaN, so the outputs (h,
+ * gates / dgates) carry NaN rather than silently wrong numbers.  A grid the
+ * device cannot hold co-resident returns MMF_ELIMIT before launch.
+ * ------------------------------------------------------------------- */
+size_t mmf_gru_sync_bytes(int32_t batch, int32_t hidden);
+int mmf_gru_forward(int32_t num_gru, int32_t batch, int32_t steps, int32_t hidden, const float* const* xproj,
+                    const float* const* w_hh, const float* const* b_hn, float* const* h, float* const* gates,
+                    void* const* sync, uint32_t* timeout, void* stream);
+int mmf_gru_backward(int32_t num_gru, int32_t batch, int32_t steps, int32_t hidden, const float* const* w_hh,
+                     const float* const* h, const float* const* gates, const float* const* dh,
+                     float* const* dgates, void* const* sync, uint32_t* timeout, void* stream);
+
+/* ---------------------------------------------------------------------
  * CNN sequence encoder's conv stack (SequenceEncoder 'cnn', src/encoders.py:87-97 / 168-175):
  *   Conv1d(in_dim, hidden, 3, padding=1) -> BatchNorm1d -> ReLU ->
  *   Conv1d(hidden, hidden, 3, padding=1) -> BatchNorm1d -> ReLU -> mean over the steps.

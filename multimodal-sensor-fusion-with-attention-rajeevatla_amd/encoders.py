@@ -27,8 +27,20 @@ time-parallel input projection and weight gradients are rocBLAS GEMMs.
 launches.  The recurrence's workgroups wait on each other: the library refuses
 a grid that cannot be co-resident, every launch gets a fresh timeout word, and
 a wait that gives up poisons its outputs with NaN; ``lstm_timed_out()`` /
-``check_lstm_timeouts()`` report such launches (one stream sync per check).  The 'gru' / 'transformer' encoder types are not on the
-path and raise NotImplementedError.
+``check_lstm_timeouts()`` report such launches (one stream sync per check).  The 'transformer'
+encoder type is not on the path and raises NotImplementedError.
+
+GRUSequenceEncoder mirrors the reference's 'gru' branch (src/encoders.py:77-85, 135-166): the same
+attributes, construction order and state_dict keys (rnn.*, projection.*), the same forward(sequence,
+lengths=None) and errors.  ``GRU`` is nn.GRU's parameter layout without being an nn.RNNBase, and
+``gru_layers`` runs every layer of several GRUs in one persistent launch (csrc/gru.hip,
+mmf_gru_forward / _backward: the LSTM's plan and inter-workgroup exchange, csrc/recurrence.h, with
+the GRU cell -- three gate rows, n depending on r inside the step, b_hn kept out of the input
+projection, a backward whose carry is d z + W_hh^T [dr, dz, dn r]).  The recurrence is fp32 FMA at
+every torch.get_float32_matmul_precision() setting, as the LSTM's.  GRU launches share the LSTM's
+timeout reporting.  SequenceEncoder(..., encoder_type="gru") itself still raises
+NotImplementedError, naming GRUSequenceEncoder; ``build_encoder`` returns the right class, and
+``encode_sequences`` batches the encoders of each recurrence kind into shared launches.
 
 ConvSequenceEncoder mirrors the reference's 'cnn' branch (src/encoders.py:87-97, 168-175:
 Conv1d(k=3, pad=1) -> BatchNorm1d -> ReLU, twice, -> AdaptiveAvgPool1d(1) -> dropout -> Linear),
@@ -151,7 +163,7 @@ def _record_timeout(flag: torch.Tensor) -> None:
 
 
 def _drain_op_flags() -> None:
-    """Fold the timeout words of the eager LSTM operator launches (mmf_ops.LSTM_FLAGS)."""
+    """Fold the timeout words of the eager LSTM / GRU operator launches (mmf_ops.LSTM_FLAGS)."""
     while _ops.LSTM_FLAGS:
         flag = _ops.LSTM_FLAGS.pop()
         if _ops.eager_tensor(flag):
@@ -159,8 +171,8 @@ def _drain_op_flags() -> None:
 
 
 def lstm_timed_out(device=None, reset: bool = True) -> bool:
-    """True if any LSTM launch on `device` since the last check gave up an inter-workgroup
-    wait.  Such a launch also writes NaN into the values it never received, so its
+    """True if any LSTM or GRU launch (both recurrences report here) on `device` since the last
+    check gave up an inter-workgroup wait.  Such a launch also writes NaN into the values it never received, so its
     encodings / gradients are NaN, never silently wrong.  Reading syncs the stream;
     call it once per step (or per epoch) rather than per launch."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -173,9 +185,9 @@ def lstm_timed_out(device=None, reset: bool = True) -> bool:
 
 
 def check_lstm_timeouts(device=None) -> None:
-    """Raise RuntimeError if an LSTM launch timed out since the last check (see lstm_timed_out)."""
+    """Raise RuntimeError if an LSTM or GRU launch timed out since the last check (see lstm_timed_out)."""
     if lstm_timed_out(device):
-        raise RuntimeError("mmfusion LSTM recurrence: an inter-workgroup wait timed out (the grid was not "
+        raise RuntimeError("mmfusion LSTM / GRU recurrence: an inter-workgroup wait timed out (the grid was not "
                            "fully co-resident); the affected encodings / gradients are NaN")
 
 
@@ -320,9 +332,12 @@ class SequenceEncoder(nn.Module):
         elif encoder_type == "cnn":
             raise NotImplementedError("encoder_type 'cnn' is served by ConvSequenceEncoder (build_encoder returns it "
                                       "for encoder_type='cnn'), not by SequenceEncoder")
-        elif encoder_type in ("gru", "transformer"):
-            raise NotImplementedError(f"encoder_type '{encoder_type}' is not on the MI355X path (only 'lstm', and "
-                                      "'cnn' through ConvSequenceEncoder / build_encoder)")
+        elif encoder_type == "gru":
+            raise NotImplementedError("encoder_type 'gru' is served by GRUSequenceEncoder (build_encoder returns it "
+                                      "for encoder_type='gru'), not by SequenceEncoder")
+        elif encoder_type == "transformer":
+            raise NotImplementedError("encoder_type 'transformer' is not on the MI355X path (build_encoder returns "
+                                      "the encoders that are)")
         else:
             raise ValueError(f"Unknown encoder type: {encoder_type}")
 
@@ -335,6 +350,153 @@ class SequenceEncoder(nn.Module):
         if self.rnn is None:
             raise RuntimeError("RNN module not initialized.")
         out = lstm_layers([self.rnn], [sequence])[0]
+        return self.encode_final_state(_final_state(out, lengths))
+
+
+# ---------------------------------------------------------------------------
+# GRUSequenceEncoder on the persistent HIP recurrence
+# ---------------------------------------------------------------------------
+
+class GRU(nn.Module):
+    """nn.GRU's constructor, attributes, parameter names / shapes / registration order and
+    initialisation (weight_ih_l{k} (3H, in), weight_hh_l{k} (3H, H), bias_ih_l{k}, bias_hh_l{k} (3H),
+    gate order r, z, n; uniform(-1/sqrt(hidden), 1/sqrt(hidden)) over the parameters in order), so the
+    same seed gives the same weights and state dicts load either way -- but not an nn.RNNBase (see
+    LSTM).  The recurrence runs on HIP (csrc/gru.hip) through gru_layers, in fp32 FMA at every
+    matmul-precision setting.  Supported: biased, unidirectional, zero initial state (the
+    reference's configuration, src/encoders.py:78-84)."""
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bias: bool = True,
+                 batch_first: bool = False, dropout: float = 0.0, bidirectional: bool = False):
+        super().__init__()
+        if not bias or bidirectional:
+            raise NotImplementedError("GRU path: biased, unidirectional")
+        if num_layers < 1:
+            raise ValueError("num_layers must be >= 1")
+        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        self.bias, self.batch_first, self.dropout = bias, batch_first, float(dropout)
+        self.bidirectional, self.proj_size = False, 0
+        for k in range(num_layers):
+            din = input_size if k == 0 else hidden_size
+            self.register_parameter(f"weight_ih_l{k}", nn.Parameter(torch.empty(3 * hidden_size, din)))
+            self.register_parameter(f"weight_hh_l{k}", nn.Parameter(torch.empty(3 * hidden_size, hidden_size)))
+            self.register_parameter(f"bias_ih_l{k}", nn.Parameter(torch.empty(3 * hidden_size)))
+            self.register_parameter(f"bias_hh_l{k}", nn.Parameter(torch.empty(3 * hidden_size)))
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        stdv = 1.0 / (self.hidden_size ** 0.5) if self.hidden_size > 0 else 0.0
+        for w in self.parameters():
+            nn.init.uniform_(w, -stdv, stdv)
+
+    def extra_repr(self) -> str:
+        s = f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}"
+        if self.batch_first:
+            s += ", batch_first=True"
+        if self.dropout:
+            s += f", dropout={self.dropout}"
+        return s
+
+    def forward(self, input: torch.Tensor, hx=None):
+        """-> output, h_n as nn.GRU (zero initial state only)."""
+        if hx is not None:
+            raise NotImplementedError("GRU path: zero initial state only")
+        if input.dim() != 3:
+            raise ValueError(f"Expected 3-D input, got shape {tuple(input.shape)}")
+        x = input if self.batch_first else input.transpose(0, 1)
+        finals: List[torch.Tensor] = []
+        out = gru_layers([self], [x], finals)[0]
+        return (out if self.batch_first else out.transpose(0, 1)), torch.stack(finals)
+
+
+def gru_layers(rnns: Sequence[nn.Module], inputs: Sequence[torch.Tensor],
+               finals: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """lstm_layers' twin: run several GRU parameter sets (batch_first inputs, zero initial state) over
+    their inputs on the HIP recurrence, every layer of all of them in one launch; returns each GRU's
+    top-layer output sequence (B, T, H).  Parameters are read by name, so an nn.GRU serves as a
+    parameter holder too.  Inter-layer dropout follows nn.GRU (training only).  With `finals`, the
+    first GRU's last h of every layer is appended to it."""
+    n = len(rnns)
+    if n == 0:
+        return []
+    H = rnns[0].hidden_size
+    layers = rnns[0].num_layers
+    for r in rnns:
+        if not r.bias or r.bidirectional or getattr(r, "proj_size", 0):
+            raise NotImplementedError("GRU path: unidirectional, biased")
+        if r.hidden_size != H or r.num_layers != layers:
+            raise ValueError("gru_layers: all GRUs need the same hidden_size and num_layers")
+    B, T = inputs[0].shape[:2]
+    for x in inputs:
+        _nat.require_device(x, "GRUSequenceEncoder input")
+        if x.shape[:2] != (B, T):
+            raise ValueError("gru_layers: all sequences need the same (batch, seq_len)")
+    cur = list(inputs)
+    for k in range(layers):
+        # time-parallel input projection on PyTorch-ROCm (xproj = x W_ih^T + b_ih + [b_hr, b_hz, 0];
+        # autograd gives dx, dW_ih, db_ih and the r, z parts of db_hh); b_hn is multiplied by r inside
+        # the cell and goes to the kernel; the recurrence is one persistent HIP launch for all GRUs
+        xproj, b_hn = [], []
+        for r, x in zip(rnns, cur):
+            x2 = _nat.f32c(x).reshape(B * T, -1)
+            b_hh = getattr(r, f"bias_hh_l{k}")
+            b = getattr(r, f"bias_ih_l{k}") + torch.cat((b_hh[:2 * H], b_hh.new_zeros(H)))
+            xproj.append(torch.addmm(b, x2, getattr(r, f"weight_ih_l{k}").t()).view(B, T, -1))
+            b_hn.append(_nat.f32c(b_hh[2 * H:]))
+        hs, _gates, flag = torch.ops.mmfusion.gru_layer_fwd(
+            xproj, [_nat.f32c(getattr(r, f"weight_hh_l{k}")) for r in rnns], b_hn)
+        if _ops.eager_tensor(flag):
+            _record_timeout(flag)
+        if finals is not None:
+            finals.append(hs[0][:, -1])
+        cur = list(hs)
+        if k + 1 < layers:
+            cur = [torch.nn.functional.dropout(o, rnns[i].dropout, rnns[i].training) for i, o in enumerate(cur)]
+    return cur
+
+
+class GRUSequenceEncoder(nn.Module):
+    """The reference SequenceEncoder's 'gru' branch (src/encoders.py:77-85, 135-166) on the HIP path: the
+    same attributes, construction order (the same seed gives the same weights) and state_dict
+    (rnn.*, projection.*).  With `lengths` the final state is read from the output at lengths - 1
+    (what packing computes), as the LSTM path does."""
+
+    encoder_type: str
+    hidden_dim: int
+    output_dim: int
+    rnn: Optional[GRU]
+    conv_net: Optional[nn.Module]
+    pool: Optional[nn.Module]
+    input_projection: Optional[nn.Linear]
+    transformer: Optional[nn.TransformerEncoder]
+    projection: nn.Module
+
+    def __init__(self, input_dim: int, hidden_dim: int = 256, output_dim: int = 128, num_layers: int = 2,
+                 dropout: float = 0.1):
+        super().__init__()
+        cast_self = cast(Any, self)
+        cast_self.encoder_type = "gru"
+        cast_self.hidden_dim = hidden_dim
+        cast_self.output_dim = output_dim
+        self.dropout_layer = nn.Dropout(dropout)
+        cast_self.conv_net = None
+        cast_self.pool = None
+        cast_self.input_projection = None
+        cast_self.transformer = None
+        self.projection = nn.Identity()   # (registered first, as in the reference: the module order)
+        cast_self.rnn = GRU(input_dim, hidden_dim, num_layers=num_layers, batch_first=True,
+                            dropout=dropout if num_layers > 1 else 0.0)
+        self.projection = nn.Linear(hidden_dim, output_dim)
+
+    def encode_final_state(self, final_state: torch.Tensor) -> torch.Tensor:
+        return self.projection(self.dropout_layer(final_state))
+
+    def forward(self, sequence: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if sequence.dim() != 3:
+            raise ValueError(f"Expected 3D input sequence, got shape {sequence.shape}")
+        if self.rnn is None:
+            raise RuntimeError("RNN module not initialized.")
+        out = gru_layers([self.rnn], [sequence])[0]
         return self.encode_final_state(_final_state(out, lengths))
 
 
@@ -437,7 +599,8 @@ def build_encoder(modality: str, input_dim: int, output_dim: int,
     """The reference's factory (src/encoders.py:400-451): the config's ``type`` ('frame' /
     'sequence' / 'mlp') decides, else the modality name (video / frames -> FrameEncoder; imu /
     audio / mocap / accelerometer / imu_* -> sequence).  A sequence encoder with
-    ``encoder_type == 'cnn'`` is a ConvSequenceEncoder, any other a SequenceEncoder.  The MLP
+    ``encoder_type == 'cnn'`` is a ConvSequenceEncoder, with 'gru' a GRUSequenceEncoder, any other a
+    SequenceEncoder.  The MLP
     encoder (type 'mlp' and unknown modalities) is not on the MI355X path."""
     config: Dict[str, Any] = dict(encoder_config) if encoder_config else {}
     kind = config.pop("type", None)
@@ -449,24 +612,44 @@ def build_encoder(modality: str, input_dim: int, output_dim: int,
         if config.get("encoder_type", "lstm") == "cnn":
             config.pop("encoder_type")
             return ConvSequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
+        if config.get("encoder_type", "lstm") == "gru":
+            config.pop("encoder_type")
+            return GRUSequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
         return SequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
     # SimpleMLPEncoder (src/encoders.py:339-397) serves config 1's EarlyFusion CPU plumbing only
     raise NotImplementedError(f"encoder for modality '{modality}' ({kind or 'mlp'}) is not on the MI355X path")
 
 
-def encode_sequences(encoders: Dict[str, SequenceEncoder], sequences: Dict[str, torch.Tensor],
+def recurrence_kind(encoder: nn.Module) -> Optional[str]:
+    """'lstm' / 'gru' for an encoder that runs on one of the persistent recurrences, else None."""
+    if isinstance(encoder, GRUSequenceEncoder):
+        return "gru"
+    if isinstance(encoder, SequenceEncoder) and encoder.encoder_type == "lstm":
+        return "lstm"
+    return None
+
+
+def encode_sequences(encoders: Dict[str, nn.Module], sequences: Dict[str, torch.Tensor],
                      lengths: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-    """{m: encoders[m](sequences[m], lengths)} with every modality's LSTM layers sharing launches
-    (the modalities of one chunk have the same (B, T))."""
+    """{m: encoders[m](sequences[m], lengths)} for SequenceEncoder ('lstm') and GRUSequenceEncoder
+    modules, with every modality's layers of one recurrence kind sharing launches (the modalities of
+    one chunk have the same (B, T)): one batched call per kind, results in the order of `sequences`."""
     names = list(sequences)
     for m in names:
         if sequences[m].dim() != 3:
             raise ValueError(f"Expected 3D input sequence, got shape {sequences[m].shape}")
-    rnns = []
+    by_kind: Dict[str, List[str]] = {}
     for m in names:
-        r = encoders[m].rnn
-        if r is None:
+        kind = recurrence_kind(encoders[m])
+        if kind is None:
+            raise TypeError(f"encode_sequences: encoder '{m}' ({type(encoders[m]).__name__}) is neither an LSTM "
+                            "SequenceEncoder nor a GRUSequenceEncoder")
+        if encoders[m].rnn is None:
             raise RuntimeError("RNN module not initialized.")
-        rnns.append(r)
-    outs = lstm_layers(rnns, [sequences[m] for m in names])
-    return {m: encoders[m].encode_final_state(_final_state(o, lengths)) for m, o in zip(names, outs)}
+        by_kind.setdefault(kind, []).append(m)
+    outs: Dict[str, torch.Tensor] = {}
+    for kind, ms in by_kind.items():
+        run = lstm_layers if kind == "lstm" else gru_layers
+        for m, o in zip(ms, run([encoders[m].rnn for m in ms], [sequences[m] for m in ms])):
+            outs[m] = o
+    return {m: encoders[m].encode_final_state(_final_state(outs[m], lengths)) for m in names}

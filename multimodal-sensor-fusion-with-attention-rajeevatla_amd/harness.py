@@ -12,8 +12,9 @@ configs that train encoders (C3 PAMAP2, C4 MHAD), one process per GPU:
     the reference's ``build_encoder`` dispatch (src/encoders.py:400-451; SequenceEncoder
     'lstm' on csrc/lstm.hip, FrameEncoder with its attention pooling on
     csrc/softmax_pool.hip, HybridFusion on the fused HIP path).  When every encoder
-    is a SequenceEncoder with one (B, T), the LSTMs of all modalities share each
-    recurrence launch (``encode_sequences``).
+    is a SequenceEncoder (or every one a GRUSequenceEncoder, csrc/gru.hip) with one
+    (B, T), the LSTMs (GRUs) of all modalities share each recurrence launch
+    (``encode_sequences``).
   * ``FlatGradBuckets`` re-points every parameter into one contiguous fp32 buffer and
     its gradient into views of another (autograd accumulates into them in place), and
     all-reduces that gradient in buckets issued from post-accumulate-grad hooks: the
@@ -99,8 +100,8 @@ class MultimodalFusionModel(nn.Module):
         for m in ds["modalities"]:
             ec = dict(mc.get("encoders", {}).get(m, {}))
             in_dim = int(ec.pop("input_dim", 64))
-            # FrameEncoder / SequenceEncoder ('lstm') / ConvSequenceEncoder ('cnn'); the MLP encoder and
-            # unknown modalities raise NotImplementedError
+            # FrameEncoder / SequenceEncoder ('lstm') / GRUSequenceEncoder ('gru') / ConvSequenceEncoder
+            # ('cnn'); the 'transformer' type, the MLP encoder and unknown modalities raise NotImplementedError
             encs[m] = build_encoder(m, in_dim, out_dim, ec)
         fusion = build_fusion_model(mc.get("fusion_type", "hybrid"), {m: out_dim for m in encs},
                                     int(ds.get("num_classes", 11)), hidden_dim=int(mc["hidden_dim"]),
@@ -108,12 +109,14 @@ class MultimodalFusionModel(nn.Module):
         return cls(encs, fusion, out_dim, bool(mc.get("layer_norm", False)))
 
     def _batched_sequences(self, features: Dict[str, torch.Tensor]) -> bool:
-        from encoders import SequenceEncoder
+        from encoders import recurrence_kind
         present = [m for m in self.encoders if m in features]
         if len(present) < 2:
             return False
         encs = [self.encoders[m] for m in present]
-        if not all(isinstance(e, SequenceEncoder) and e.rnn is not None for e in encs):
+        # all LSTM SequenceEncoders or all GRUSequenceEncoders: one launch per layer for all of them
+        kinds = {recurrence_kind(e) for e in encs}
+        if len(kinds) != 1 or None in kinds or any(e.rnn is None for e in encs):
             return False
         r0 = encs[0].rnn
         shapes = {tuple(features[m].shape[:2]) for m in present}

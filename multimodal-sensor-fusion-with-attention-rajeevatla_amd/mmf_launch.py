@@ -29,8 +29,8 @@ first on ``sys.path``, ``sys.argv[0]`` = the script, ``__name__ == "__main__"`` 
 
 ``--mmf-encoders`` (opt-in): after importing the reference's ``encoders``
 module, route its ``FrameEncoder.attention_pool`` (src/encoders.py:313-336) and the
-'lstm' branch of ``SequenceEncoder.forward`` (src/encoders.py:135-166) through this
-package's HIP kernels (csrc/softmax_pool.hip, csrc/lstm.hip).  The modules, their
+'lstm' and 'gru' branches of ``SequenceEncoder.forward`` (src/encoders.py:135-166) through this
+package's HIP kernels (csrc/softmax_pool.hip, csrc/lstm.hip, csrc/gru.hip).  The modules, their
 parameters and state-dict keys stay the reference's own; other encoder types and
 pooling strategies run the reference's code.
 
@@ -82,9 +82,10 @@ def install(encoders: bool = False) -> None:
 
 
 def patch_encoders(ref_encoders) -> None:
-    """Route the reference's FrameEncoder.attention_pool and SequenceEncoder's 'lstm' forward through
-    this package's HIP kernels (same arguments, same results as the package's own encoders, which are
-    pinned to the reference's outputs: tests/test_gpu_softmax_pool.py, tests/test_gpu_lstm.py)."""
+    """Route the reference's FrameEncoder.attention_pool and SequenceEncoder's 'lstm' / 'gru' forward
+    through this package's HIP kernels (same arguments, same results as the package's own encoders,
+    which are pinned to the reference's outputs: tests/test_gpu_softmax_pool.py, tests/test_gpu_lstm.py,
+    tests/test_gpu_gru.py)."""
     mmf_enc = sys.modules.get("mmf_encoders") or _load("mmf_encoders", "encoders.py")
     if getattr(ref_encoders, "_mmf_patched", False):
         return
@@ -98,13 +99,14 @@ def patch_encoders(ref_encoders) -> None:
     ref_seq_forward = se.forward
 
     def forward(self, sequence, lengths=None):
-        if self.encoder_type != "lstm":
+        if self.encoder_type not in ("lstm", "gru"):
             return ref_seq_forward(self, sequence, lengths)
         if sequence.dim() != 3:
             raise ValueError(f"Expected 3D input sequence, got shape {sequence.shape}")
         if self.rnn is None:
             raise RuntimeError("RNN module not initialized.")
-        out = mmf_enc.lstm_layers([self.rnn], [sequence])[0]   # (the module's own nn.LSTM parameters)
+        layers = mmf_enc.lstm_layers if self.encoder_type == "lstm" else mmf_enc.gru_layers
+        out = layers([self.rnn], [sequence])[0]   # (the module's own nn.LSTM / nn.GRU parameters)
         return self.projection(self.dropout_layer(mmf_enc._final_state(out, lengths)))
 
     fe.attention_pool = attention_pool

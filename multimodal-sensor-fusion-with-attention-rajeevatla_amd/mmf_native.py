@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "mmf_late_fusion_workspace_bytes", "mmf_late_fusion_forward", "mmf_late_fusion_backward",
     "mmf_gather_chunks",
     "mmf_lstm_sync_bytes", "mmf_lstm_forward", "mmf_lstm_backward",
+    "mmf_gru_sync_bytes", "mmf_gru_forward", "mmf_gru_backward",
     "mmf_mc_reduce", "mmf_hybrid_mc_forward", "mmf_temperature_nll_workspace_bytes", "mmf_temperature_nll",
     "mmf_uncertainty_fusion_forward", "mmf_uncertainty_fusion_backward",
     "mmf_conv_encoder_workspace_bytes", "mmf_conv_encoder_forward", "mmf_conv_encoder_backward",
@@ -218,6 +219,12 @@ def lib() -> ctypes.CDLL:
     L.mmf_lstm_forward.restype = c_int32
     L.mmf_lstm_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mmf_lstm_backward.restype = c_int32
+    L.mmf_gru_sync_bytes.argtypes = [c_int32, c_int32]
+    L.mmf_gru_sync_bytes.restype = c_size_t
+    L.mmf_gru_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mmf_gru_forward.restype = c_int32
+    L.mmf_gru_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mmf_gru_backward.restype = c_int32
     L.mmf_mc_reduce.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, vp, vp]
     L.mmf_mc_reduce.restype = c_int32
     L.mmf_hybrid_mc_forward.argtypes = [POINTER(HybridDesc), POINTER(HybridParams), vp, vp, vp, c_int32, vp, vp, vp,

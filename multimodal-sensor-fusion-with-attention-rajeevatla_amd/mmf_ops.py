@@ -24,6 +24,7 @@ Operators (csrc entry point, reference interface):
   attention_pool_fwd / _bwd        mmf_attention_pool_*              src/encoders.py:313-336
   late_weights_fwd / _bwd          mmf_late_fusion_*                 src/fusion.py:228-245
   lstm_layer_fwd / _bwd            mmf_lstm_forward / _backward      src/encoders.py:135-166
+  gru_layer_fwd / _bwd             mmf_gru_forward / _backward       src/encoders.py:77-85, 135-166
   mc_reduce                        mmf_mc_reduce                     src/uncertainty.py:58-66, 487-491
   temperature_nll                  mmf_temperature_nll               src/uncertainty.py:431-435
   uncertainty_fusion_fwd / _bwd    mmf_uncertainty_fusion_*          src/uncertainty.py:305-362
@@ -832,9 +833,99 @@ def _lstm_backward(ctx, dhs, _dcs, _dgates, _dflag):
 
 lstm_layer_fwd.register_autograd(_lstm_backward, setup_context=_lstm_setup)
 
-# timeout words of the eager LSTM launches, drained by encoders.lstm_timed_out (a compiled
-# graph keeps only the NaN poisoning of values that never arrived, csrc/lstm.hip)
+# timeout words of the eager LSTM and GRU launches, drained by encoders.lstm_timed_out (a compiled
+# graph keeps only the NaN poisoning of values that never arrived, csrc/lstm.hip, csrc/gru.hip)
 LSTM_FLAGS: List[Tensor] = []
+
+
+# ============================================================================ GRU layer (GRUSequenceEncoder)
+@torch.library.custom_op("mmfusion::gru_layer_fwd", mutates_args=(), device_types="cuda")
+def gru_layer_fwd(xproj: List[Tensor], w_hh: List[Tensor],
+                  b_hn: List[Tensor]) -> Tuple[List[Tensor], List[Tensor], Tensor]:
+    """One layer of n independent GRUs: xproj (B, T, 3H) = x W_ih^T + b_ih + [b_hr, b_hz, 0] per GRU ->
+    h (B, T, H), gates (B, T, 4H) = (r, z, n, q = W_hn h + b_hn) per GRU, and the launch's timeout
+    word.  fp32 FMA at every matmul-precision setting, as the LSTM."""
+    L = _nat.lib()
+    n = len(xproj)
+    dev = xproj[0].device
+    B, T, H3 = xproj[0].shape
+    H = H3 // 3
+    hs = [torch.empty(B, T, H, dtype=torch.float32, device=dev) for _ in range(n)]
+    gates = [torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev) for _ in range(n)]
+    sync = torch.empty(n, L.mmf_gru_sync_bytes(B, H), dtype=torch.uint8, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    rc = L.mmf_gru_forward(
+        n, B, T, H, _nat.ptr_array([t.data_ptr() for t in xproj]), _nat.ptr_array([w.data_ptr() for w in w_hh]),
+        _nat.ptr_array([b.data_ptr() for b in b_hn]), _nat.ptr_array([t.data_ptr() for t in hs]),
+        _nat.ptr_array([t.data_ptr() for t in gates]), _nat.ptr_array([sync[i].data_ptr() for i in range(n)]),
+        flag.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "GRU forward")
+    return hs, gates, flag
+
+
+@gru_layer_fwd.register_fake
+def _(xproj, w_hh, b_hn):
+    B, T, H3 = xproj[0].shape
+    H = H3 // 3
+    n = len(xproj)
+    x0 = xproj[0]
+    return ([x0.new_empty(B, T, H) for _ in range(n)], [x0.new_empty(B, T, 4 * H) for _ in range(n)],
+            x0.new_empty(1, dtype=torch.int32))
+
+
+@torch.library.custom_op("mmfusion::gru_layer_bwd", mutates_args=(), device_types="cuda")
+def gru_layer_bwd(w_hh: List[Tensor], hs: List[Tensor], gates: List[Tensor],
+                  dh: List[Tensor]) -> Tuple[List[Tensor], Tensor]:
+    """-> dgates (B, T, 4H) = (dr_pre, dz_pre, dn_pre, dn_pre * r) per GRU and the timeout word."""
+    L = _nat.lib()
+    n = len(w_hh)
+    dev = hs[0].device
+    B, T, H = hs[0].shape
+    dgates = [torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev) for _ in range(n)]
+    sync = torch.empty(n, L.mmf_gru_sync_bytes(B, H), dtype=torch.uint8, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    rc = L.mmf_gru_backward(
+        n, B, T, H, _nat.ptr_array([w.data_ptr() for w in w_hh]), _nat.ptr_array([t.data_ptr() for t in hs]),
+        _nat.ptr_array([t.data_ptr() for t in gates]),
+        _nat.ptr_array([d.data_ptr() if d.numel() else 0 for d in dh]),
+        _nat.ptr_array([t.data_ptr() for t in dgates]), _nat.ptr_array([sync[i].data_ptr() for i in range(n)]),
+        flag.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "GRU backward")
+    return dgates, flag
+
+
+@gru_layer_bwd.register_fake
+def _(w_hh, hs, gates, dh):
+    B, T, H = hs[0].shape
+    return [hs[0].new_empty(B, T, 4 * H) for _ in w_hh], hs[0].new_empty(1, dtype=torch.int32)
+
+
+def _gru_setup(ctx, inputs, output):
+    xproj, w_hh, _b_hn = inputs
+    hs, gates, _flag = output
+    ctx.n = len(xproj)
+    ctx.save_for_backward(*w_hh, *hs, *gates)
+
+
+def _gru_backward(ctx, dhs, _dgates, _dflag):
+    n = ctx.n
+    sv = ctx.saved_tensors
+    w_hh, hs, gates = (list(sv[k * n:(k + 1) * n]) for k in range(3))
+    dh = [hs[i].new_empty(0) if (dhs is None or dhs[i] is None) else dhs[i].contiguous() for i in range(n)]
+    dgates, flag = torch.ops.mmfusion.gru_layer_bwd(w_hh, hs, gates, dh)
+    if eager_tensor(flag):
+        LSTM_FLAGS.append(flag)
+    B, T, H = hs[0].shape
+    dxproj = [dg[..., :3 * H] for dg in dgates]
+    # dgh = d(W_hh h_{t-1} + [0, 0, b_hn]) = (dr_pre, dz_pre, dn_pre * r)
+    dgh = [torch.cat((dg[..., :2 * H], dg[..., 3 * H:]), dim=-1) for dg in dgates]
+    # dW_hh = sum_t dgh_t^T h_{t-1} (h_{-1} = 0)
+    dw_hh = [dgh[i][:, 1:].reshape(-1, 3 * H).t() @ hs[i][:, :-1].reshape(-1, H) for i in range(n)]
+    db_hn = [dgh[i][..., 2 * H:].reshape(-1, H).sum(0) for i in range(n)]
+    return dxproj, dw_hh, db_hn
+
+
+gru_layer_fwd.register_autograd(_gru_backward, setup_context=_gru_setup)
 
 
 def eager_tensor(t: Tensor) -> bool:
