@@ -137,15 +137,10 @@ class FrameEncoder(nn.Module):
 
 
 # ---------------------------------------------------------------------------
-# SequenceEncoder (LSTM) on the persistent HIP recurrence
+# LSTM, GRU and SequenceEncoder (LSTM) on the persistent HIP recurrence
 # ---------------------------------------------------------------------------
 
 _LSTM_TIMEOUT: Dict[int, torch.Tensor] = {}
-
-
-def _timeout_flag(dev: torch.device) -> torch.Tensor:
-    """A fresh timeout word for one LSTM launch (the library zeroes it on the stream)."""
-    return torch.zeros(1, dtype=torch.int32, device=dev)
 
 
 def _timeout_acc(dev: torch.device) -> torch.Tensor:
@@ -191,32 +186,35 @@ def check_lstm_timeouts(device=None) -> None:
                            "fully co-resident); the affected encodings / gradients are NaN")
 
 
-class LSTM(nn.Module):
-    """nn.LSTM's constructor, attributes, parameter names / shapes / registration order and
-    initialisation (uniform(-1/sqrt(hidden), 1/sqrt(hidden)) over the parameters in order), so
-    the same seed gives the same weights and state dicts load either way -- but not an
-    nn.RNNBase: TorchDynamo refuses to trace RNNBase modules at all ("Attempted to wrap RNN"),
-    which would break the reference's torch.compile of its encoders (src/train.py:203-214).
-    The recurrence runs on HIP (csrc/lstm.hip) through lstm_layers.  Supported: biased,
-    unidirectional, no projection, zero initial state (the reference's configuration,
-    src/encoders.py:68-76)."""
+class _Recurrent(nn.Module):
+    """What LSTM and GRU share: torch's constructor arguments and attributes, the parameter names /
+    shapes / registration order of nn.LSTM / nn.GRU (GATES * hidden rows per weight and bias) and its
+    initialisation (uniform(-1/sqrt(hidden), 1/sqrt(hidden)) over the parameters in order), so the same
+    seed gives the same weights and state dicts load either way -- but not an nn.RNNBase: TorchDynamo
+    refuses to trace RNNBase modules at all ("Attempted to wrap RNN"), which would break the
+    reference's torch.compile of its encoders (src/train.py:203-214)."""
+
+    GATES: int            # gate rows per hidden unit
+    KIND: str             # "LSTM" / "GRU" in the messages
+    SUPPORTED: str        # what the constructor accepts
 
     def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bias: bool = True,
-                 batch_first: bool = False, dropout: float = 0.0, bidirectional: bool = False, proj_size: int = 0):
+                 batch_first: bool = False, dropout: float = 0.0, bidirectional: bool = False):
         super().__init__()
-        if not bias or bidirectional or proj_size:
-            raise NotImplementedError("LSTM path: biased, unidirectional, no projection")
+        if not bias or bidirectional:
+            raise NotImplementedError(f"{self.KIND} path: {self.SUPPORTED}")
         if num_layers < 1:
             raise ValueError("num_layers must be >= 1")
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.bias, self.batch_first, self.dropout = bias, batch_first, float(dropout)
         self.bidirectional, self.proj_size = False, 0
+        rows = self.GATES * hidden_size
         for k in range(num_layers):
             din = input_size if k == 0 else hidden_size
-            self.register_parameter(f"weight_ih_l{k}", nn.Parameter(torch.empty(4 * hidden_size, din)))
-            self.register_parameter(f"weight_hh_l{k}", nn.Parameter(torch.empty(4 * hidden_size, hidden_size)))
-            self.register_parameter(f"bias_ih_l{k}", nn.Parameter(torch.empty(4 * hidden_size)))
-            self.register_parameter(f"bias_hh_l{k}", nn.Parameter(torch.empty(4 * hidden_size)))
+            self.register_parameter(f"weight_ih_l{k}", nn.Parameter(torch.empty(rows, din)))
+            self.register_parameter(f"weight_hh_l{k}", nn.Parameter(torch.empty(rows, hidden_size)))
+            self.register_parameter(f"bias_ih_l{k}", nn.Parameter(torch.empty(rows)))
+            self.register_parameter(f"bias_hh_l{k}", nn.Parameter(torch.empty(rows)))
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -232,61 +230,135 @@ class LSTM(nn.Module):
             s += f", dropout={self.dropout}"
         return s
 
-    def forward(self, input: torch.Tensor, hx=None):
-        """-> output, (h_n, c_n) as nn.LSTM (zero initial state only).  c_n carries no gradient:
-        the recurrence's backward takes d(h) only, which is all the encoders use."""
+    def _run(self, input: torch.Tensor, hx) -> tuple:
+        """-> the output sequence in the input's layout and the last state of every layer."""
         if hx is not None:
-            raise NotImplementedError("LSTM path: zero initial state only")
+            raise NotImplementedError(f"{self.KIND} path: zero initial state only")
         if input.dim() != 3:
             raise ValueError(f"Expected 3-D input, got shape {tuple(input.shape)}")
         x = input if self.batch_first else input.transpose(0, 1)
-        finals: List[tuple] = []
-        out = lstm_layers([self], [x], finals)[0]
-        h_n = torch.stack([h for h, _ in finals])
-        c_n = torch.stack([c for _, c in finals]).detach()
-        return (out if self.batch_first else out.transpose(0, 1)), (h_n, c_n)
+        finals: list = []
+        out = _recurrent_layers(self.KIND, [self], [x], finals)[0]
+        return (out if self.batch_first else out.transpose(0, 1)), finals
 
 
-def lstm_layers(rnns: Sequence[LSTM], inputs: Sequence[torch.Tensor],
-                finals: Optional[List[tuple]] = None) -> List[torch.Tensor]:
-    """Run several LSTM parameter sets (batch_first inputs, zero initial state) over their inputs on
-    the HIP recurrence, every layer of all of them in one launch; returns each LSTM's top-layer
-    output sequence (B, T, H).  Inter-layer dropout follows nn.LSTM (training only).  With
-    `finals`, the first LSTM's last (h, c) of every layer is appended to it."""
-    n = len(rnns)
-    if n == 0:
+class LSTM(_Recurrent):
+    """nn.LSTM's layout (see _Recurrent; gate order i, f, g, o).  The recurrence runs on HIP
+    (csrc/lstm.hip) through lstm_layers.  Supported: biased, unidirectional, no projection, zero
+    initial state (the reference's configuration, src/encoders.py:68-76)."""
+
+    GATES, KIND, SUPPORTED = 4, "LSTM", "biased, unidirectional, no projection"
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bias: bool = True,
+                 batch_first: bool = False, dropout: float = 0.0, bidirectional: bool = False, proj_size: int = 0):
+        if proj_size:
+            raise NotImplementedError(f"LSTM path: {self.SUPPORTED}")
+        super().__init__(input_size, hidden_size, num_layers, bias, batch_first, dropout, bidirectional)
+
+    def forward(self, input: torch.Tensor, hx=None):
+        """-> output, (h_n, c_n) as nn.LSTM (zero initial state only).  c_n carries no gradient:
+        the recurrence's backward takes d(h) only, which is all the encoders use."""
+        out, finals = self._run(input, hx)
+        return out, (torch.stack([h for h, _ in finals]), torch.stack([c for _, c in finals]).detach())
+
+
+class GRU(_Recurrent):
+    """nn.GRU's layout (see _Recurrent; weight_ih_l{k} (3H, in), weight_hh_l{k} (3H, H), bias_ih_l{k},
+    bias_hh_l{k} (3H), gate order r, z, n).  The recurrence runs on HIP (csrc/gru.hip) through
+    gru_layers, in fp32 FMA at every matmul-precision setting.  Supported: biased, unidirectional,
+    zero initial state (the reference's configuration, src/encoders.py:78-84)."""
+
+    GATES, KIND, SUPPORTED = 3, "GRU", "biased, unidirectional"
+
+    def forward(self, input: torch.Tensor, hx=None):
+        """-> output, h_n as nn.GRU (zero initial state only)."""
+        out, finals = self._run(input, hx)
+        return out, torch.stack(finals)
+
+
+def _input_projection(r: nn.Module, x: torch.Tensor, k: int, bias: torch.Tensor) -> torch.Tensor:
+    """Layer k's time-parallel x W_ih^T + bias on PyTorch-ROCm (autograd gives dx, dW_ih and the
+    gradient of what was folded into `bias`): (B, T, in) -> (B, T, GATES * H)."""
+    B, T = x.shape[:2]
+    return torch.addmm(bias, _nat.f32c(x).reshape(B * T, -1), getattr(r, f"weight_ih_l{k}").t()).view(B, T, -1)
+
+
+def _lstm_layer(rnns, xs, k: int):
+    """xproj = x W_ih^T + b_ih + b_hh; -> every LSTM's h, the timeout word, the first LSTM's last (h, c)."""
+    xproj = [_input_projection(r, x, k, getattr(r, f"bias_ih_l{k}") + getattr(r, f"bias_hh_l{k}"))
+             for r, x in zip(rnns, xs)]
+    hs, cs, _gates, flag = torch.ops.mmfusion.lstm_layer_fwd(
+        xproj, [_nat.f32c(getattr(r, f"weight_hh_l{k}")) for r in rnns])
+    return hs, flag, (hs[0][:, -1], cs[0][:, -1])
+
+
+def _gru_layer(rnns, xs, k: int):
+    """xproj = x W_ih^T + b_ih + [b_hr, b_hz, 0] (autograd also gives the r, z parts of db_hh); b_hn is
+    multiplied by r inside the cell and goes to the kernel; -> every GRU's h, the timeout word, the
+    first GRU's last h."""
+    H = rnns[0].hidden_size
+    xproj, b_hn = [], []
+    for r, x in zip(rnns, xs):
+        b_hh = getattr(r, f"bias_hh_l{k}")
+        b = getattr(r, f"bias_ih_l{k}") + torch.cat((b_hh[:2 * H], b_hh.new_zeros(H)))
+        xproj.append(_input_projection(r, x, k, b))
+        b_hn.append(_nat.f32c(b_hh[2 * H:]))
+    hs, _gates, flag = torch.ops.mmfusion.gru_layer_fwd(
+        xproj, [_nat.f32c(getattr(r, f"weight_hh_l{k}")) for r in rnns], b_hn)
+    return hs, flag, hs[0][:, -1]
+
+
+# per recurrence kind: its layer, what its messages call the routine and the input, what it supports
+_LAYERS = {"LSTM": (_lstm_layer, "lstm_layers", "SequenceEncoder input", "unidirectional, biased, no projection"),
+           "GRU": (_gru_layer, "gru_layers", "GRUSequenceEncoder input", "unidirectional, biased")}
+
+
+def _recurrent_layers(kind: str, rnns: Sequence[nn.Module], inputs: Sequence[torch.Tensor],
+                      finals: Optional[list]) -> List[torch.Tensor]:
+    """lstm_layers / gru_layers: every layer of all `rnns` as one persistent HIP launch per layer."""
+    layer, name, what, supported = _LAYERS[kind]
+    if len(rnns) == 0:
         return []
     H = rnns[0].hidden_size
     layers = rnns[0].num_layers
     for r in rnns:
-        if not r.bias or r.bidirectional or r.proj_size:
-            raise NotImplementedError("LSTM path: unidirectional, biased, no projection")
+        if not r.bias or r.bidirectional or getattr(r, "proj_size", 0):
+            raise NotImplementedError(f"{kind} path: {supported}")
         if r.hidden_size != H or r.num_layers != layers:
-            raise ValueError("lstm_layers: all LSTMs need the same hidden_size and num_layers")
+            raise ValueError(f"{name}: all {kind}s need the same hidden_size and num_layers")
     B, T = inputs[0].shape[:2]
     for x in inputs:
-        _nat.require_device(x, "SequenceEncoder input")
+        _nat.require_device(x, what)
         if x.shape[:2] != (B, T):
-            raise ValueError("lstm_layers: all sequences need the same (batch, seq_len)")
+            raise ValueError(f"{name}: all sequences need the same (batch, seq_len)")
     cur = list(inputs)
     for k in range(layers):
-        # time-parallel input projection on PyTorch-ROCm (xproj = x W_ih^T + b_ih + b_hh; autograd
-        # gives dx, dW_ih, db), the recurrence as one persistent HIP launch for all LSTMs
-        xproj = []
-        for r, x in zip(rnns, cur):
-            x2 = _nat.f32c(x).reshape(B * T, -1)
-            b = getattr(r, f"bias_ih_l{k}") + getattr(r, f"bias_hh_l{k}")
-            xproj.append(torch.addmm(b, x2, getattr(r, f"weight_ih_l{k}").t()).view(B, T, -1))
-        hs, cs, _gates, flag = torch.ops.mmfusion.lstm_layer_fwd(
-            xproj, [_nat.f32c(getattr(r, f"weight_hh_l{k}")) for r in rnns])
+        hs, flag, final = layer(rnns, cur, k)
         if _ops.eager_tensor(flag):
             _record_timeout(flag)
         if finals is not None:
-            finals.append((hs[0][:, -1], cs[0][:, -1]))
+            finals.append(final)
         cur = list(hs)
         if k + 1 < layers:
             cur = [torch.nn.functional.dropout(o, rnns[i].dropout, rnns[i].training) for i, o in enumerate(cur)]
     return cur
+
+
+def lstm_layers(rnns: Sequence[nn.Module], inputs: Sequence[torch.Tensor],
+                finals: Optional[List[tuple]] = None) -> List[torch.Tensor]:
+    """Run several LSTM parameter sets (batch_first inputs, zero initial state) over their inputs on
+    the HIP recurrence, every layer of all of them in one launch; returns each LSTM's top-layer
+    output sequence (B, T, H).  Parameters are read by name, so an nn.LSTM serves as a parameter
+    holder too.  Inter-layer dropout follows nn.LSTM (training only).  With `finals`, the first
+    LSTM's last (h, c) of every layer is appended to it."""
+    return _recurrent_layers("LSTM", rnns, inputs, finals)
+
+
+def gru_layers(rnns: Sequence[nn.Module], inputs: Sequence[torch.Tensor],
+               finals: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """lstm_layers' twin for GRU parameter sets (or nn.GRU modules); with `finals`, the first GRU's
+    last h of every layer is appended to it."""
+    return _recurrent_layers("GRU", rnns, inputs, finals)
 
 
 def _final_state(out: torch.Tensor, lengths: Optional[torch.Tensor]) -> torch.Tensor:
@@ -351,108 +423,6 @@ class SequenceEncoder(nn.Module):
             raise RuntimeError("RNN module not initialized.")
         out = lstm_layers([self.rnn], [sequence])[0]
         return self.encode_final_state(_final_state(out, lengths))
-
-
-# ---------------------------------------------------------------------------
-# GRUSequenceEncoder on the persistent HIP recurrence
-# ---------------------------------------------------------------------------
-
-class GRU(nn.Module):
-    """nn.GRU's constructor, attributes, parameter names / shapes / registration order and
-    initialisation (weight_ih_l{k} (3H, in), weight_hh_l{k} (3H, H), bias_ih_l{k}, bias_hh_l{k} (3H),
-    gate order r, z, n; uniform(-1/sqrt(hidden), 1/sqrt(hidden)) over the parameters in order), so the
-    same seed gives the same weights and state dicts load either way -- but not an nn.RNNBase (see
-    LSTM).  The recurrence runs on HIP (csrc/gru.hip) through gru_layers, in fp32 FMA at every
-    matmul-precision setting.  Supported: biased, unidirectional, zero initial state (the
-    reference's configuration, src/encoders.py:78-84)."""
-
-    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bias: bool = True,
-                 batch_first: bool = False, dropout: float = 0.0, bidirectional: bool = False):
-        super().__init__()
-        if not bias or bidirectional:
-            raise NotImplementedError("GRU path: biased, unidirectional")
-        if num_layers < 1:
-            raise ValueError("num_layers must be >= 1")
-        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
-        self.bias, self.batch_first, self.dropout = bias, batch_first, float(dropout)
-        self.bidirectional, self.proj_size = False, 0
-        for k in range(num_layers):
-            din = input_size if k == 0 else hidden_size
-            self.register_parameter(f"weight_ih_l{k}", nn.Parameter(torch.empty(3 * hidden_size, din)))
-            self.register_parameter(f"weight_hh_l{k}", nn.Parameter(torch.empty(3 * hidden_size, hidden_size)))
-            self.register_parameter(f"bias_ih_l{k}", nn.Parameter(torch.empty(3 * hidden_size)))
-            self.register_parameter(f"bias_hh_l{k}", nn.Parameter(torch.empty(3 * hidden_size)))
-        self.reset_parameters()
-
-    def reset_parameters(self) -> None:
-        stdv = 1.0 / (self.hidden_size ** 0.5) if self.hidden_size > 0 else 0.0
-        for w in self.parameters():
-            nn.init.uniform_(w, -stdv, stdv)
-
-    def extra_repr(self) -> str:
-        s = f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}"
-        if self.batch_first:
-            s += ", batch_first=True"
-        if self.dropout:
-            s += f", dropout={self.dropout}"
-        return s
-
-    def forward(self, input: torch.Tensor, hx=None):
-        """-> output, h_n as nn.GRU (zero initial state only)."""
-        if hx is not None:
-            raise NotImplementedError("GRU path: zero initial state only")
-        if input.dim() != 3:
-            raise ValueError(f"Expected 3-D input, got shape {tuple(input.shape)}")
-        x = input if self.batch_first else input.transpose(0, 1)
-        finals: List[torch.Tensor] = []
-        out = gru_layers([self], [x], finals)[0]
-        return (out if self.batch_first else out.transpose(0, 1)), torch.stack(finals)
-
-
-def gru_layers(rnns: Sequence[nn.Module], inputs: Sequence[torch.Tensor],
-               finals: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
-    """lstm_layers' twin: run several GRU parameter sets (batch_first inputs, zero initial state) over
-    their inputs on the HIP recurrence, every layer of all of them in one launch; returns each GRU's
-    top-layer output sequence (B, T, H).  Parameters are read by name, so an nn.GRU serves as a
-    parameter holder too.  Inter-layer dropout follows nn.GRU (training only).  With `finals`, the
-    first GRU's last h of every layer is appended to it."""
-    n = len(rnns)
-    if n == 0:
-        return []
-    H = rnns[0].hidden_size
-    layers = rnns[0].num_layers
-    for r in rnns:
-        if not r.bias or r.bidirectional or getattr(r, "proj_size", 0):
-            raise NotImplementedError("GRU path: unidirectional, biased")
-        if r.hidden_size != H or r.num_layers != layers:
-            raise ValueError("gru_layers: all GRUs need the same hidden_size and num_layers")
-    B, T = inputs[0].shape[:2]
-    for x in inputs:
-        _nat.require_device(x, "GRUSequenceEncoder input")
-        if x.shape[:2] != (B, T):
-            raise ValueError("gru_layers: all sequences need the same (batch, seq_len)")
-    cur = list(inputs)
-    for k in range(layers):
-        # time-parallel input projection on PyTorch-ROCm (xproj = x W_ih^T + b_ih + [b_hr, b_hz, 0];
-        # autograd gives dx, dW_ih, db_ih and the r, z parts of db_hh); b_hn is multiplied by r inside
-        # the cell and goes to the kernel; the recurrence is one persistent HIP launch for all GRUs
-        xproj, b_hn = [], []
-        for r, x in zip(rnns, cur):
-            x2 = _nat.f32c(x).reshape(B * T, -1)
-            b_hh = getattr(r, f"bias_hh_l{k}")
-            b = getattr(r, f"bias_ih_l{k}") + torch.cat((b_hh[:2 * H], b_hh.new_zeros(H)))
-            xproj.append(torch.addmm(b, x2, getattr(r, f"weight_ih_l{k}").t()).view(B, T, -1))
-            b_hn.append(_nat.f32c(b_hh[2 * H:]))
-        hs, _gates, flag = torch.ops.mmfusion.gru_layer_fwd(
-            xproj, [_nat.f32c(getattr(r, f"weight_hh_l{k}")) for r in rnns], b_hn)
-        if _ops.eager_tensor(flag):
-            _record_timeout(flag)
-        if finals is not None:
-            finals.append(hs[0][:, -1])
-        cur = list(hs)
-        if k + 1 < layers:
-            cur = [torch.nn.functional.dropout(o, rnns[i].dropout, rnns[i].training) for i, o in enumerate(cur)]
-    return cur
 
 
 class GRUSequenceEncoder(nn.Module):

@@ -213,18 +213,12 @@ def lib() -> ctypes.CDLL:
     L.mmf_gather_chunks.argtypes = [vp, c_int64, c_int32, vp, vp, c_int32, c_int32, c_int32, vp, vp, vp, c_int32,
                                      vp, vp, vp]
     L.mmf_gather_chunks.restype = c_int32
-    L.mmf_lstm_sync_bytes.argtypes = [c_int32, c_int32]
-    L.mmf_lstm_sync_bytes.restype = c_size_t
-    L.mmf_lstm_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mmf_lstm_forward.restype = c_int32
-    L.mmf_lstm_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mmf_lstm_backward.restype = c_int32
-    L.mmf_gru_sync_bytes.argtypes = [c_int32, c_int32]
-    L.mmf_gru_sync_bytes.restype = c_size_t
-    L.mmf_gru_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mmf_gru_forward.restype = c_int32
-    L.mmf_gru_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mmf_gru_backward.restype = c_int32
+    for cell in ("lstm", "gru"):   # the two recurrences: (n, B, T, H), 8 pointers each way
+        sync_bytes = getattr(L, f"mmf_{cell}_sync_bytes")
+        sync_bytes.argtypes, sync_bytes.restype = [c_int32, c_int32], c_size_t
+        for way in ("forward", "backward"):
+            fn = getattr(L, f"mmf_{cell}_{way}")
+            fn.argtypes, fn.restype = [c_int32] * 4 + [vp] * 8, c_int32
     L.mmf_mc_reduce.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, vp, vp]
     L.mmf_mc_reduce.restype = c_int32
     L.mmf_hybrid_mc_forward.argtypes = [POINTER(HybridDesc), POINTER(HybridParams), vp, vp, vp, c_int32, vp, vp, vp,

@@ -749,27 +749,46 @@ def _lw_backward(ctx, dfused, _dweights):
 late_weights_fwd.register_autograd(_lw_backward, setup_context=_lw_setup)
 
 
-# ============================================================================ LSTM layer (SequenceEncoder)
+# ============================================================================ LSTM / GRU layers (the persistent recurrences)
+# timeout words of the eager LSTM and GRU launches, drained by encoders.lstm_timed_out (a compiled
+# graph keeps only the NaN poisoning of values that never arrived, csrc/recurrence.h)
+LSTM_FLAGS: List[Tensor] = []
+
+
+def _recurrence(cell: str, way: str, B: int, T: int, H: int, ins: Sequence[Sequence[Tensor]],
+                widths: Sequence[int]) -> Tuple[List[List[Tensor]], Tensor]:
+    """One launch of mmf_{cell}_{way} for the n networks of a layer.  `ins`: the per-network input lists
+    in the prototype's order (an empty tensor goes as NULL); the outputs follow them there, one list
+    of n (B, T, w) tensors per w in `widths`.  Allocates the outputs, the sync granules and the
+    launch's timeout word; -> (outputs, timeout word)."""
+    L = _nat.lib()
+    n, dev = len(ins[0]), ins[0][0].device
+    outs = [[torch.empty(B, T, w, dtype=torch.float32, device=dev) for _ in range(n)] for w in widths]
+    sync = torch.empty(n, getattr(L, f"mmf_{cell}_sync_bytes")(B, H), dtype=torch.uint8, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    arrays = [_nat.ptr_array([t.data_ptr() if t.numel() else 0 for t in ts]) for ts in (*ins, *outs, sync)]
+    rc = getattr(L, f"mmf_{cell}_{way}")(n, B, T, H, *arrays, flag.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, f"{cell.upper()} {way}")
+    return outs, flag
+
+
+def _recurrence_dgates(bwd_op, w_hh: List[Tensor], state: List[Tensor], gates: List[Tensor], dhs) -> List[Tensor]:
+    """The autograd formulas' call of lstm_layer_bwd / gru_layer_bwd: `state` is what the cell saved
+    beside its gates (c / h); where autograd has no d(h) an empty tensor stands for zeros."""
+    dh = [s.new_empty(0) if (dhs is None or dhs[i] is None) else dhs[i].contiguous() for i, s in enumerate(state)]
+    dgates, flag = bwd_op(w_hh, state, gates, dh)
+    if eager_tensor(flag):
+        LSTM_FLAGS.append(flag)
+    return dgates
+
+
 @torch.library.custom_op("mmfusion::lstm_layer_fwd", mutates_args=(), device_types="cuda")
 def lstm_layer_fwd(xproj: List[Tensor], w_hh: List[Tensor]) -> Tuple[List[Tensor], List[Tensor], List[Tensor], Tensor]:
     """One layer of n independent LSTMs: xproj (B, T, 4H) = x W_ih^T + b_ih + b_hh per LSTM ->
     h, c (B, T, H), activated gates (B, T, 4H) per LSTM, and the launch's timeout word."""
-    L = _nat.lib()
-    n = len(xproj)
-    dev = xproj[0].device
     B, T, H4 = xproj[0].shape
     H = H4 // 4
-    hs = [torch.empty(B, T, H, dtype=torch.float32, device=dev) for _ in range(n)]
-    cs = [torch.empty(B, T, H, dtype=torch.float32, device=dev) for _ in range(n)]
-    gates = [torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev) for _ in range(n)]
-    sync = torch.empty(n, L.mmf_lstm_sync_bytes(B, H), dtype=torch.uint8, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = L.mmf_lstm_forward(
-        n, B, T, H, _nat.ptr_array([t.data_ptr() for t in xproj]), _nat.ptr_array([w.data_ptr() for w in w_hh]),
-        _nat.ptr_array([t.data_ptr() for t in hs]), _nat.ptr_array([t.data_ptr() for t in cs]),
-        _nat.ptr_array([t.data_ptr() for t in gates]), _nat.ptr_array([sync[i].data_ptr() for i in range(n)]),
-        flag.data_ptr(), _nat.stream_ptr(dev))
-    _nat.check(rc, "LSTM forward")
+    (hs, cs, gates), flag = _recurrence("lstm", "forward", B, T, H, (xproj, w_hh), (H, H, 4 * H))
     return hs, cs, gates, flag
 
 
@@ -787,20 +806,8 @@ def _(xproj, w_hh):
 def lstm_layer_bwd(w_hh: List[Tensor], cs: List[Tensor], gates: List[Tensor],
                    dh: List[Tensor]) -> Tuple[List[Tensor], Tensor]:
     """-> d(pre-activation gates) (B, T, 4H) per LSTM (= d xproj) and the timeout word."""
-    L = _nat.lib()
-    n = len(w_hh)
-    dev = cs[0].device
     B, T, H = cs[0].shape
-    dgates = [torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev) for _ in range(n)]
-    sync = torch.empty(n, L.mmf_lstm_sync_bytes(B, H), dtype=torch.uint8, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = L.mmf_lstm_backward(
-        n, B, T, H, _nat.ptr_array([w.data_ptr() for w in w_hh]), _nat.ptr_array([t.data_ptr() for t in cs]),
-        _nat.ptr_array([t.data_ptr() for t in gates]),
-        _nat.ptr_array([d.data_ptr() if d.numel() else 0 for d in dh]),
-        _nat.ptr_array([t.data_ptr() for t in dgates]), _nat.ptr_array([sync[i].data_ptr() for i in range(n)]),
-        flag.data_ptr(), _nat.stream_ptr(dev))
-    _nat.check(rc, "LSTM backward")
+    (dgates,), flag = _recurrence("lstm", "backward", B, T, H, (w_hh, cs, gates, dh), (4 * H,))
     return dgates, flag
 
 
@@ -821,10 +828,7 @@ def _lstm_backward(ctx, dhs, _dcs, _dgates, _dflag):
     n = ctx.n
     sv = ctx.saved_tensors
     w_hh, hs, cs, gates = (list(sv[k * n:(k + 1) * n]) for k in range(4))
-    dh = [hs[i].new_empty(0) if (dhs is None or dhs[i] is None) else dhs[i].contiguous() for i in range(n)]
-    dgates, flag = torch.ops.mmfusion.lstm_layer_bwd(w_hh, cs, gates, dh)
-    if eager_tensor(flag):
-        LSTM_FLAGS.append(flag)
+    dgates = _recurrence_dgates(torch.ops.mmfusion.lstm_layer_bwd, w_hh, cs, gates, dhs)
     B, T, H = hs[0].shape
     # dW_hh = sum_t dgates_t^T h_{t-1} (h_{-1} = 0)
     dw_hh = [dgates[i][:, 1:].reshape(-1, 4 * H).t() @ hs[i][:, :-1].reshape(-1, H) for i in range(n)]
@@ -833,33 +837,16 @@ def _lstm_backward(ctx, dhs, _dcs, _dgates, _dflag):
 
 lstm_layer_fwd.register_autograd(_lstm_backward, setup_context=_lstm_setup)
 
-# timeout words of the eager LSTM and GRU launches, drained by encoders.lstm_timed_out (a compiled
-# graph keeps only the NaN poisoning of values that never arrived, csrc/lstm.hip, csrc/gru.hip)
-LSTM_FLAGS: List[Tensor] = []
 
-
-# ============================================================================ GRU layer (GRUSequenceEncoder)
 @torch.library.custom_op("mmfusion::gru_layer_fwd", mutates_args=(), device_types="cuda")
 def gru_layer_fwd(xproj: List[Tensor], w_hh: List[Tensor],
                   b_hn: List[Tensor]) -> Tuple[List[Tensor], List[Tensor], Tensor]:
     """One layer of n independent GRUs: xproj (B, T, 3H) = x W_ih^T + b_ih + [b_hr, b_hz, 0] per GRU ->
     h (B, T, H), gates (B, T, 4H) = (r, z, n, q = W_hn h + b_hn) per GRU, and the launch's timeout
     word.  fp32 FMA at every matmul-precision setting, as the LSTM."""
-    L = _nat.lib()
-    n = len(xproj)
-    dev = xproj[0].device
     B, T, H3 = xproj[0].shape
     H = H3 // 3
-    hs = [torch.empty(B, T, H, dtype=torch.float32, device=dev) for _ in range(n)]
-    gates = [torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev) for _ in range(n)]
-    sync = torch.empty(n, L.mmf_gru_sync_bytes(B, H), dtype=torch.uint8, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = L.mmf_gru_forward(
-        n, B, T, H, _nat.ptr_array([t.data_ptr() for t in xproj]), _nat.ptr_array([w.data_ptr() for w in w_hh]),
-        _nat.ptr_array([b.data_ptr() for b in b_hn]), _nat.ptr_array([t.data_ptr() for t in hs]),
-        _nat.ptr_array([t.data_ptr() for t in gates]), _nat.ptr_array([sync[i].data_ptr() for i in range(n)]),
-        flag.data_ptr(), _nat.stream_ptr(dev))
-    _nat.check(rc, "GRU forward")
+    (hs, gates), flag = _recurrence("gru", "forward", B, T, H, (xproj, w_hh, b_hn), (H, 4 * H))
     return hs, gates, flag
 
 
@@ -877,20 +864,8 @@ def _(xproj, w_hh, b_hn):
 def gru_layer_bwd(w_hh: List[Tensor], hs: List[Tensor], gates: List[Tensor],
                   dh: List[Tensor]) -> Tuple[List[Tensor], Tensor]:
     """-> dgates (B, T, 4H) = (dr_pre, dz_pre, dn_pre, dn_pre * r) per GRU and the timeout word."""
-    L = _nat.lib()
-    n = len(w_hh)
-    dev = hs[0].device
     B, T, H = hs[0].shape
-    dgates = [torch.empty(B, T, 4 * H, dtype=torch.float32, device=dev) for _ in range(n)]
-    sync = torch.empty(n, L.mmf_gru_sync_bytes(B, H), dtype=torch.uint8, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = L.mmf_gru_backward(
-        n, B, T, H, _nat.ptr_array([w.data_ptr() for w in w_hh]), _nat.ptr_array([t.data_ptr() for t in hs]),
-        _nat.ptr_array([t.data_ptr() for t in gates]),
-        _nat.ptr_array([d.data_ptr() if d.numel() else 0 for d in dh]),
-        _nat.ptr_array([t.data_ptr() for t in dgates]), _nat.ptr_array([sync[i].data_ptr() for i in range(n)]),
-        flag.data_ptr(), _nat.stream_ptr(dev))
-    _nat.check(rc, "GRU backward")
+    (dgates,), flag = _recurrence("gru", "backward", B, T, H, (w_hh, hs, gates, dh), (4 * H,))
     return dgates, flag
 
 
@@ -911,10 +886,7 @@ def _gru_backward(ctx, dhs, _dgates, _dflag):
     n = ctx.n
     sv = ctx.saved_tensors
     w_hh, hs, gates = (list(sv[k * n:(k + 1) * n]) for k in range(3))
-    dh = [hs[i].new_empty(0) if (dhs is None or dhs[i] is None) else dhs[i].contiguous() for i in range(n)]
-    dgates, flag = torch.ops.mmfusion.gru_layer_bwd(w_hh, hs, gates, dh)
-    if eager_tensor(flag):
-        LSTM_FLAGS.append(flag)
+    dgates = _recurrence_dgates(torch.ops.mmfusion.gru_layer_bwd, w_hh, hs, gates, dhs)
     B, T, H = hs[0].shape
     dxproj = [dg[..., :3 * H] for dg in dgates]
     # dgh = d(W_hh h_{t-1} + [0, 0, b_hn]) = (dr_pre, dz_pre, dn_pre * r)

@@ -1,8 +1,8 @@
 """SequenceEncoder LSTM on the persistent HIP recurrence (SURVEY §8f rank 3,
 src/encoders.py:34-166): the module against fixtures the reference produced
 (tests/golden/gen_golden.py, SEQENC_CASES), the raw C-ABI recurrence against
-the CPU oracle (oracle/lstm_cpu.py) including batch instances of <= 4 rows and
-several LSTMs per launch, and the C3 shape (T = 1024, H = 256) at full length.
+the CPU oracle (oracle/lstm_cpu.py) including T = 1, batch instances of <= 4 rows,
+several LSTMs per launch and a NULL dh, and the C3 shape (T = 1024, H = 256) at full length.
 Tolerance: 1e-3 relative (BASELINE.json fp32 parity)."""
 import ctypes
 
@@ -59,7 +59,7 @@ def test_lstm_limits_cpu(nat):
 
 
 def _run_recurrence(nat, enc_mod, xproj_l, w_hh_l, dh_l):
-    """Raw C-ABI forward + backward for n LSTMs on cuda:0."""
+    """Raw C-ABI forward + backward for n LSTMs on cuda:0; a None entry of dh_l is passed as NULL."""
     L = nat.lib()
     dev = torch.device("cuda", 0)
     n = len(xproj_l)
@@ -72,11 +72,11 @@ def _run_recurrence(nat, enc_mod, xproj_l, w_hh_l, dh_l):
     g = [torch.empty(B, T, 4 * H, device=dev) for _ in range(n)]
     sync = [torch.empty(L.mmf_lstm_sync_bytes(B, H), dtype=torch.uint8, device=dev) for _ in range(n)]
     tmo = torch.zeros(1, dtype=torch.int32, device=dev)
-    arr = lambda ts: nat.ptr_array([t.data_ptr() for t in ts])  # noqa: E731
+    arr = lambda ts: nat.ptr_array([t.data_ptr() if t is not None else 0 for t in ts])  # noqa: E731
     st = nat.stream_ptr(dev)
     rc = L.mmf_lstm_forward(n, B, T, H, arr(xp), arr(wh), arr(h), arr(c), arr(g), arr(sync), tmo.data_ptr(), st)
     assert rc == 0, nat.lib().mmf_last_error()
-    dh = [torch.from_numpy(d.astype(np.float32)).to(dev) for d in dh_l]
+    dh = [torch.from_numpy(d.astype(np.float32)).to(dev) if d is not None else None for d in dh_l]
     dg = [torch.empty(B, T, 4 * H, device=dev) for _ in range(n)]
     rc = L.mmf_lstm_backward(n, B, T, H, arr(wh), arr(c), arr(g), arr(dh), arr(dg), arr(sync), tmo.data_ptr(), st)
     assert rc == 0, nat.lib().mmf_last_error()
@@ -87,7 +87,7 @@ def _run_recurrence(nat, enc_mod, xproj_l, w_hh_l, dh_l):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,B,T,H", [(1, 1, 7, 64), (3, 5, 33, 64), (2, 4, 20, 192), (4, 9, 16, 256)])
+@pytest.mark.parametrize("n,B,T,H", [(1, 1, 7, 64), (1, 2, 1, 128), (3, 5, 33, 64), (2, 4, 20, 192), (4, 9, 16, 256)])
 def test_recurrence_matches_oracle(nat, enc_mod, n, B, T, H):
     from oracle.lstm_cpu import lstm_backward, lstm_forward
     rng = np.random.default_rng(1000 * n + B + T + H)
@@ -109,6 +109,21 @@ def test_recurrence_matches_oracle(nat, enc_mod, n, B, T, H):
         assert rel_err(torch.from_numpy(cs[i]), c) <= TOL, i
         assert rel_err(torch.from_numpy(gs[i]), g) <= TOL, i
         assert rel_err(torch.from_numpy(dgs[i]), dg) <= TOL, i
+
+
+@pytest.mark.gpu
+def test_null_dh_equals_zeros(nat, enc_mod):
+    """A NULL dh entry is a zero upstream gradient."""
+    n, B, T, H = 2, 3, 9, 64
+    rng = np.random.default_rng(5)
+    bound = 1.0 / np.sqrt(H)
+    xp = [rng.standard_normal((B, T, 4 * H)).astype(np.float32) for _ in range(n)]
+    w = [rng.uniform(-bound, bound, size=(4 * H, H)).astype(np.float32) for _ in range(n)]
+    dh = rng.standard_normal((B, T, H)).astype(np.float32)
+    with_null = _run_recurrence(nat, enc_mod, xp, w, [dh, None])[3]
+    with_zero = _run_recurrence(nat, enc_mod, xp, w, [dh, np.zeros_like(dh)])[3]
+    assert np.array_equal(with_null[0], with_zero[0]) and np.array_equal(with_null[1], with_zero[1])
+    assert not with_null[1].any() and with_null[0].any()
 
 
 @pytest.mark.gpu
