@@ -67,13 +67,14 @@ int main(void) {{
     assert out == py
 
 
-def _desc(nat, **kw):
+def _desc(nat, modalities=3, in_dim=16, pairs=None, **kw):
     d = nat.HybridDesc()
-    d.batch, d.num_modalities, d.hidden, d.num_heads, d.num_classes = 4, 3, 32, 4, 5
-    for m in range(3):
+    d.batch, d.num_modalities, d.hidden, d.num_heads, d.num_classes = 4, modalities, 32, 4, 5
+    for m in range(modalities):
         d.seq_len[m] = 0
-        d.in_dim[m] = 16
-    pairs = [(q, k) for q in range(3) for k in range(3) if q != k]
+        d.in_dim[m] = in_dim
+    if pairs is None:
+        pairs = [(q, k) for q in range(modalities) for k in range(modalities) if q != k]
     d.num_pairs = len(pairs)
     for g, (q, k) in enumerate(pairs):
         d.pair_q[g], d.pair_k[g] = q, k
@@ -154,6 +155,34 @@ def test_lean_l1_query(nat):
     assert L.mmf_hybrid_lean_l1(ctypes.byref(d)) == 0
     assert L.mmf_hybrid_lean_l1(ctypes.byref(_desc(nat, matmul_precision=nat.PRECISION_MEDIUM))) == 0
     assert L.mmf_hybrid_lean_l1(ctypes.byref(_desc(nat, num_heads=3))) == 0   # invalid descriptor
+
+
+def test_lean_l1_eligibility_boundary(nat, monkeypatch):
+    """mmf_hybrid_lean_l1 at the edges of the envelope lean_l1_desc admits: M = 2..4 with every
+    ordered pair present exactly once, H % 4 == 0 up to 128, each D_m % 4 == 0 up to 128, up to 16
+    classes, up to 8 heads."""
+    monkeypatch.delenv("MMF_NO_L1_LEAN", raising=False)
+    L = nat.lib()
+
+    def lean(**kw):
+        return L.mmf_hybrid_lean_l1(ctypes.byref(_desc(nat, **kw)))
+
+    full3 = [(q, k) for q in range(3) for k in range(3) if q != k]
+    assert lean(modalities=4) == 1                       # all 12 pairs
+    assert lean(modalities=5) == 0
+    assert lean(hidden=128) == 1
+    assert lean(hidden=132) == 0
+    assert lean(hidden=30, num_heads=2) == 0
+    assert lean(in_dim=128) == 1
+    assert lean(in_dim=132) == 0
+    assert lean(in_dim=6) == 0
+    assert lean(num_classes=16) == 1
+    assert lean(num_classes=17) == 0
+    assert lean(hidden=128, num_heads=8) == 1
+    assert lean(hidden=128, num_heads=16) == 0
+    assert lean(pairs=full3) == 1
+    assert lean(pairs=full3[:-1]) == 0                   # one pair missing
+    assert lean(pairs=full3[:-1] + [full3[0]]) == 0      # one pair duplicated in place of another
 
 
 PLAN_KNOBS = ("MMF_PSTORE", "MMF_NO_LONG_FUSED", "MMF_NO_FUSED_BWD", "MMF_NO_BF16_QK", "MMF_NO_GEMM_B16",

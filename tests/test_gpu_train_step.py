@@ -15,6 +15,8 @@ import math
 import pytest
 import torch
 
+from _l1 import _three_calls
+
 pytestmark = pytest.mark.gpu
 
 M, B, L, D, H, HEADS, C = 3, 8, 6, 16, 16, 2, 5
@@ -193,26 +195,6 @@ def test_accumulate_rejects_uneven_micro_batches(mods):
     with pytest.raises(ValueError, match="equal micro-batches"):
         train_step.HybridTrainStep(_model(fusion, 0.0).cuda(), [f.cuda() for f in feats], mask.cuda(), labels.cuda(),
                                    accumulate=3)
-
-
-def _three_calls(st, nat):
-    """The split path the one-call step replaces: mmf_hybrid_forward -> mmf_cross_entropy_ls ->
-    mmf_hybrid_backward on the step's own buffers (accumulate = 1)."""
-    import ctypes
-    L = nat.lib()
-    d = st.plan.desc
-    s = nat.stream_ptr(st.dev)
-    rc = L.mmf_hybrid_forward(ctypes.byref(d), ctypes.byref(st.pstruct), ctypes.cast(st.xarr[0], ctypes.c_void_p),
-                              st.mask.data_ptr(), st.rng.data_ptr(), st.saved.data_ptr(), st.logits.data_ptr(),
-                              st.fw.data_ptr(), None, s)
-    nat.check(rc, "forward")
-    rc = L.mmf_cross_entropy_ls(st.mask.size(0), d.num_classes, st.logits.data_ptr(), st.labels.data_ptr(),
-                                st.smoothing, 1.0, st.losses.data_ptr(), st.dlogits.data_ptr(), s)
-    nat.check(rc, "cross-entropy")
-    rc = L.mmf_hybrid_backward(ctypes.byref(d), ctypes.byref(st.pstruct), ctypes.cast(st.xarr[0], ctypes.c_void_p),
-                               st.mask.data_ptr(), st.saved.data_ptr(), st.dlogits.data_ptr(), st.ws.data_ptr(),
-                               ctypes.byref(st.gstruct), ctypes.cast(st.dxarr[0], ctypes.c_void_p), s)
-    nat.check(rc, "backward")
 
 
 @pytest.mark.parametrize("seq", [False, True])
