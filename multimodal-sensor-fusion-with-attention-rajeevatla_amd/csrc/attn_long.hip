@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "mmf_device.h"
+#include "mmf_env.h"
 
 namespace mmf {
 
@@ -908,7 +909,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_poolL_fwd_fused_bf16(const At
 }  // namespace
 
 bool attn_long_fused_ok(const AttnPair* pairs, int npairs, int hd, float drop_p) {
-  if (getenv("MMF_NO_LONG_FUSED")) return false;
+  if (switch_set<SW_NO_LONG_FUSED>()) return false;
   if (math_mode() != 1 || hd > 64 || hd % 4 != 0 || npairs <= 0) return false;
   for (int i = 0; i < npairs; ++i) {
     const AttnPair& P = pairs[i];
@@ -923,7 +924,7 @@ bool attn_long_fused_ok(const AttnPair* pairs, int npairs, int hd, float drop_p)
 }
 
 bool attn_long_fwd_ok(const AttnPair* pairs, int npairs, int hd, float drop_p, const RngSnap* rng) {
-  if (getenv("MMF_NO_LONG_FUSED")) return false;
+  if (switch_set<SW_NO_LONG_FUSED>()) return false;
   if (math_mode() != 1 || hd > 64 || hd % 4 != 0 || npairs <= 0) return false;
   if (drop_p > 0.f && !rng) return false;
   for (int i = 0; i < npairs; ++i) {
@@ -1015,7 +1016,7 @@ hipError_t launch_attn_long_fused_fwd(const AttnPair* pairs, int npairs, int B, 
     }
     const dim3 grid((unsigned)(B * heads), (unsigned)n);
     // 16 waves (one key tile each at Lk = 512); MMF_LONG_FWD_W8=1: the 8-wave form (A/B)
-    static const bool w8 = getenv("MMF_LONG_FWD_W8") != nullptr;
+    const bool w8 = switch_set<SW_LONG_FWD_W8>();
     const char* kn = w8 ? (drop ? "attn_poolL_fwd_fused_bf16<true, 8>" : "attn_poolL_fwd_fused_bf16<false, 8>")
                         : (drop ? "attn_poolL_fwd_fused_bf16<true, 16>" : "attn_poolL_fwd_fused_bf16<false, 16>");
     ProfLaunch prof_(st, kn, fl, by);

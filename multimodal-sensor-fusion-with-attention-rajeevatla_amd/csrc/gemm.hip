@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "mmf_device.h"
+#include "mmf_env.h"
 
 namespace mmf {
 
@@ -59,7 +60,7 @@ struct TileCtx {
 // (the default: C5 projections 2.58 -> 2.47 ms/step; the split-K weight gradients were
 // slower interleaved, 2.00 -> 2.27 ms), 2 every launch.  MMF_GEMM_ILV overrides.
 int gemm_interleave_mode() {
-  const char* e = getenv("MMF_GEMM_ILV");
+  const char* e = switch_value<SW_GEMM_ILV>();
   if (!e || !e[0]) return 1;
   return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
 }
@@ -1656,7 +1657,7 @@ bool job_wsr(const GemmJob& J, int amode, int bmode) {
   // workgroup, its register-resident W^T loaded per workgroup) took 75 / 75 us and the step
   // 0.959-0.972 -> 0.984-0.998 ms (profiles/r06/wsr_epi/).  It pays with many tiles per
   // workgroup (the Q / K projections: 3072 tiles), not here.
-  static const bool ext_on = getenv("MMF_WSR_EPI") != nullptr;
+  const bool ext_on = switch_set<SW_WSR_EPI>();
   if (!ext_on && (bmode != MODE_RK || (g.epi & ~(EPI_BIAS | EPI_RELU)))) return false;
   // one row scale per 128-row tile (a scalar load); column sums per tile into colsum
   if ((g.epi & EPI_ROWSCALE) && (g.rs_div <= 0 || g.rs_div % BM != 0 || !g.rowscale)) return false;
@@ -1749,7 +1750,7 @@ hipError_t launch_gemm(const GemmJob* jobs_in, int njobs, int amode, int bmode, 
     bool wsr = njobs > 0;
     for (int i = 0; i < njobs && wsr; ++i)
       wsr = job_wsr(jobs_in[i], amode, bmode) && jobs_in[i].src[0].K == jobs_in[0].src[0].K && !jobs_in[i].chain;
-    if (wsr && getenv("MMF_NO_WSR") == nullptr) return launch_wsr(jobs_in, njobs, st, rng_advance, bmode, drop_p, rng);
+    if (wsr && !switch_set<SW_NO_WSR>()) return launch_wsr(jobs_in, njobs, st, rng_advance, bmode, drop_p, rng);
   }
   // the tiled launches below take the rng advance on their first launch; a call that
   // ends in small slabs only advances with a launch of its own
@@ -2071,7 +2072,7 @@ bool job_wsr_b16(const GemmJob& J) {
 hipError_t launch_wsr_b16(const GemmJob* jobs, int njobs, hipStream_t st) {
   // 8-wave workgroups over 256-column groups when every job is 256 wide (MMF_WSR16_W4=1: 4 waves
   // over 128-column groups, A/B)
-  static const bool w4 = getenv("MMF_WSR16_W4") != nullptr;
+  const bool w4 = switch_set<SW_WSR16_W4>();
   bool w8 = !w4;
   for (int i = 0; i < njobs && w8; ++i) w8 = jobs[i].g.N % (2 * BN) == 0;
   const int cw = w8 ? 2 * BN : BN;
@@ -2123,7 +2124,7 @@ hipError_t launch_wsr_b16(const GemmJob* jobs, int njobs, hipStream_t st) {
     }
     const int grid = std::min(items, 2 * cu_count());
     // ring depth: 9 tiles (72 KB: two workgroups per CU), MMF_WSR16_NS=6 the first form (A/B)
-    const char* ns = getenv("MMF_WSR16_NS");
+    const char* ns = switch_value<SW_WSR16_NS>();
     if (ns && ns[0] == '6') {
       ProfLaunch prof_(st, "gemm_wsr_b16_kernel<6>", fl, by);
       mmf_launch(gemm_wsr_b16_kernel<6>, dim3(grid), dim3(NT), 0, st, args, items, K);
@@ -2140,7 +2141,7 @@ hipError_t launch_wsr_b16(const GemmJob* jobs, int njobs, hipStream_t st) {
 hipError_t launch_gemm_b16(const GemmJob* jobs_in, int njobs, hipStream_t st, int amode, int bmode, float drop_p,
                            const RngSnap* rng, uint64_t* rng_advance) {
   if (njobs <= 0) return rng_advance ? launch_rng_advance(rng_advance, st) : hipSuccess;
-  if (amode == MODE_RK && bmode == MODE_RK && !getenv("MMF_NO_WSR16")) {
+  if (amode == MODE_RK && bmode == MODE_RK && !switch_set<SW_NO_WSR16>()) {
     bool wsr = true;
     for (int i = 0; i < njobs && wsr; ++i) wsr = job_wsr_b16(jobs_in[i]);
     if (wsr) {
@@ -2187,8 +2188,8 @@ hipError_t launch_gemm_b16(const GemmJob* jobs_in, int njobs, hipStream_t st, in
   // Round 5, with dZ on bf16 output and gate: RK x KR calls whose every contraction is >= 1 024
   // (dZ: K = 10 H at C5) take them too -- dZ 0.96 -> 0.92 ms, while dX (K = H) measured 0.21 -> 0.23
   // with them and keeps 128 x 128 (profiles/r05/c5_wide_dz_long/)
-  static const bool no_wide = getenv("MMF_GEMM_NO_WIDE") != nullptr;
-  static const bool wide_dz = getenv("MMF_GEMM_WIDE_DZ") != nullptr;
+  const bool no_wide = switch_set<SW_GEMM_NO_WIDE>();
+  const bool wide_dz = switch_set<SW_GEMM_WIDE_DZ>();
   double kmin = 1e30;
   for (int i = 0; i < njobs; ++i) kmin = std::min(kmin, work[i]);
   bool wide = !no_wide && (form == 2 || (form == 3 && (wide_dz || (!any_partial && kmin >= 1024.0))));

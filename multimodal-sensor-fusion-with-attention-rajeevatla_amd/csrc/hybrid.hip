@@ -16,49 +16,246 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <unistd.h>
 
 #include "capi_util.h"
+#include "mmf_env.h"
 
 using namespace mmf;
 
 namespace {
 
-// The plan switches read from the environment on every call (A/B and diagnostic knobs: they pick
-// kernels and so the `saved` / `workspace` layouts).  Their fingerprint is what a caller stores in
-// mmf_hybrid_desc.plan_flags when it sizes its buffers; an entry point whose current fingerprint
-// differs refuses to run (MMF_EINVAL) instead of laying its buffers out differently from how the
-// caller sized them (MMF_PSTORE set after HybridTrainStep allocated `saved`
-// overflowed it).  The sum of per-entry FNV-1a hashes of "NAME=VALUE": independent of the order
-// of `environ`, and 0 with none of them set.
-const char* const kPlanKnobs[] = {
-    "MMF_PSTORE", "MMF_NO_LONG_FUSED", "MMF_NO_FUSED_BWD", "MMF_NO_BF16_QK", "MMF_NO_GEMM_B16",
-    "MMF_QK_CAT", "MMF_NO_DQK_B16", "MMF_NO_PROJ_B16", "MMF_NO_PCOL", "MMF_NO_POOLE", "MMF_POOLE_FLAT",
-    "MMF_NO_L1_LEAN", "MMF_WGRAD_SPLIT_CAP", "MMF_NO_SIDE_STREAM", "MMF_SIDE_STREAM", "MMF_KW_SERIAL",
-    "MMF_KW_FUSED", "MMF_NO_KW_FUSED", "MMF_NO_GATE_B16", "MMF_POOL_PER_PAIR", "MMF_TAIL_S"};
+inline int Lm(const mmf_hybrid_desc* d, int m) { return d->seq_len[m] > 0 ? d->seq_len[m] : 1; }
+inline int kw_ld(int lk) { return lk <= 128 ? 4 : (lk + 31) / 32; }
 
-uint32_t plan_flags_now() {
-  uint32_t sum = 0;
-  for (char** e = environ; e && *e; ++e) {
-    const char* s = *e;
-    if (std::strncmp(s, "MMF_", 4) != 0) continue;
-    for (const char* k : kPlanKnobs) {
-      const size_t n = std::strlen(k);
-      if (std::strncmp(s, k, n) != 0 || s[n] != '=') continue;
-      uint32_t h = 2166136261u;
-      for (const char* c = s; *c; ++c) h = (h ^ (uint8_t)*c) * 16777619u;
-      sum += h | 1u;   // (never 0 for a set knob)
-      break;
+// SINGLE_KEY: the pair attends over ONE key (2-D inputs, the reference's own case, or a 3-D key of
+// length 1): softmax over one key is the mask indicator, so the pair has no Q / K /
+// QK^T work and its query_proj / key_proj gradients are exactly zero (single_key.hip).
+// WIDE: head_dim beyond the fused attention kernels' register budget (MMF_MAX_HEAD_DIM): the pair's
+// scores are materialised and contracted by GEMMs (wide.hip).
+// ATTN: the attention kernels.
+enum PairKind : uint8_t { PAIR_SINGLE_KEY, PAIR_WIDE, PAIR_ATTN };
+inline PairKind pair_kind(int lk, int hd) {
+  return lk == 1 ? PAIR_SINGLE_KEY : (hd > MMF_MAX_HEAD_DIM ? PAIR_WIDE : PAIR_ATTN);
+}
+
+// Where the attention dropout keep words of the pooled plan's attention pairs are drawn (they
+// depend only on the rng snapshot): INLINE by the attention forward itself; SERIAL by a launch on
+// the call's stream ahead of the projection GEMM; SIDE_STREAM by that launch on a side stream,
+// beside the projection GEMMs; MASK_FOLD by extra workgroups of the input-mask kernel.
+enum class KeepWords : uint8_t { INLINE, SERIAL, SIDE_STREAM, MASK_FOLD };
+// (the pairs the input-mask kernel can draw for: whole 32-key words)
+inline bool kw_foldable(int lk) { return lk > 0 && lk % 32 == 0 && kw_ld(lk) >= lk / 32; }
+
+// Every decision that shapes one HybridFusion call -- which kernels run and how `saved` and the
+// workspace are laid out -- resolved once per entry point from the descriptor and the plan
+// switches (resolve_plan) and handed down.  Nothing below resolve_plan reads a switch.
+struct HybridPlan {
+  uint32_t flags;                     // plan_fingerprint() of the switches this plan was resolved under
+  PairKind kind[MMF_MAX_PAIRS];
+  bool pair_qk_bf16[MMF_MAX_PAIRS];   // the pair's Q / K are stored as bf16
+  bool drop;                          // training with dropout > 0
+  bool pool, tail;                    // the pooled plan; its fused per-sample tail (with >= 1 pair)
+  bool pstore, qk_gemm_b16, qk_cat, dqk_b16, proj_b16;
+  bool pcol_in_proj[MMF_MAX_MODALITIES], poole_in_dz[MMF_MAX_MODALITIES];
+  int32_t qcol[MMF_MAX_PAIRS], kcol[MMF_MAX_PAIRS], ncat[MMF_MAX_MODALITIES];   // qk_cat: the column slots
+  bool lean_l1, l1_full;              // the descriptor half of lean_l1(); the C2 shape of its kernels
+  int split_cap;                      // cap on a weight gradient's split count (0: none)
+  bool dx_chain, gate_b16, fused_bwd;
+  KeepWords keep_words;
+  bool kw_fold_unfit;                 // MMF_KW_FUSED asked for MASK_FOLD and the pairs do not fit it
+
+  bool sk(int g) const { return kind[g] == PAIR_SINGLE_KEY; }
+  bool wide(int g) const { return kind[g] == PAIR_WIDE; }
+  bool attn(int g) const { return kind[g] == PAIR_ATTN; }
+};
+
+HybridPlan resolve_plan(const mmf_hybrid_desc* d) {
+  HybridPlan p;
+  memset(&p, 0, sizeof(p));
+  p.flags = plan_fingerprint();
+  const int M = d->num_modalities, H = d->hidden, nh = d->num_heads, hd = H / nh, np = d->num_pairs;
+  const bool medium = d->matmul_precision == MMF_PRECISION_MEDIUM;
+  p.drop = d->training && d->dropout > 0.f;
+
+  // Pooled plan (attention.hip "Pooled-output attention"): keys up to 128 run the
+  // one-chunk kernels, longer keys the streamed long-key kernels; the pooled
+  // helpers keep heads x Lk query-mean probabilities in LDS (pool.hip POOL_PB_CAP).
+  p.pool = nh <= 8;
+  bool long_keys = false;   // (of any pair)
+  bool attn_long = false;   // (of an attention-kernel pair)
+  int nattn = 0;
+  for (int g = 0; g < np; ++g) {
+    const int lk = Lm(d, d->pair_k[g]);
+    p.kind[g] = pair_kind(lk, hd);
+    if (lk * nh > POOL_PB_CAP) p.pool = false;
+    long_keys = long_keys || lk > 128;
+    if (p.attn(g)) {
+      ++nattn;
+      attn_long = attn_long || lk > 128;
     }
   }
-  return sum;
+  p.tail = np && p.pool && !long_keys && tail_supported(M, H, d->num_classes, nh, hd, np);
+
+  // Training forward keeps the pre-dropout probabilities for the fused backward (no S recompute
+  // there): the pooled plan with every attention-kernel pair inside the lean fused kernels' shape
+  // (attn_pstore_ok).  All pairs or none (one launch each way).  Opt-in (MMF_PSTORE=1): measured
+  // at C2 it costs more than it saves (the 402 MB blob's write and read slow the
+  // neighbouring kernels more than the skipped recompute gains).
+  p.pstore = d->training && p.pool && nattn > 0 && switch_set<SW_PSTORE>();
+  for (int g = 0; g < np && p.pstore; ++g)
+    if (p.attn(g) && (!attn_pstore_ok(Lm(d, d->pair_q[g]), Lm(d, d->pair_k[g]), 1, hd) || H % 4 != 0))
+      p.pstore = false;
+
+  // "medium" long-key pairs on the one-pass kernels (attn_long.hip) keep Q and K in bf16: the
+  // Q/K GEMM rounds its output once (EPI_BF16) -- exactly the rounding the kernels applied when
+  // they loaded fp32 rows -- so the GEMM writes and the attention kernels read half the bytes.
+  // All long pairs or none (the one-pass launches take every long pair); off with
+  // return_attention (the attention-map kernels read fp32 Q / K) and whenever the streamed
+  // kernels could run (MMF_NO_LONG_FUSED, MMF_NO_FUSED_BWD; MMF_NO_BF16_QK: fp32 Q / K, A/B).
+  p.fused_bwd = !switch_set<SW_NO_FUSED_BWD>();
+  bool qk_bf16 = medium && p.pool && !d->return_attention && !switch_set<SW_NO_LONG_FUSED>() && p.fused_bwd &&
+                 !switch_set<SW_NO_BF16_QK>() && hd <= 64 && hd % 8 == 0 && H % 8 == 0 && attn_long;
+  for (int g = 0; g < np && qk_bf16; ++g) {
+    const int lk = Lm(d, d->pair_k[g]);
+    if (p.attn(g) && lk > 128 && (lk > 512 || lk % 32 != 0)) qk_bf16 = false;
+  }
+  int nb16 = 0;
+  for (int g = 0; g < np; ++g) {
+    p.pair_qk_bf16[g] = qk_bf16 && p.attn(g) && Lm(d, d->pair_k[g]) > 128;
+    nb16 += p.pair_qk_bf16[g];
+  }
+
+  // The Q/K projection GEMM on bf16 copies of both operands ("medium", every Q/K pair stores bf16
+  // Q / K): the projection GEMM's epilogue also writes P_m as bf16 (EPI_BF16COPY) and the pairs'
+  // W_q / W_k are converted once per forward; the GEMM (launch_gemm_b16) then streams half the
+  // operand bytes and feeds its MFMAs without conversions.  MMF_NO_GEMM_B16=1: the fp32-operand form.
+  p.qk_gemm_b16 = medium && !switch_set<SW_NO_GEMM_B16>() && H % 8 == 0 && nattn > 0 && nb16 == nattn &&
+                  2 * nattn <= CVT_MAX;
+
+  // The Q / K projections concatenated per modality ("medium", qk_gemm_b16): modality m's Q (pairs
+  // with query m) and K (pairs with key m) are column blocks of one (B L_m) x (ncat_m H) bf16 matrix,
+  // written by ONE bf16 GEMM of P_m against the stacked W_q / W_k copies (C5: 6 GEMMs of N = 2 560 in
+  // place of 60 of N = 256, each P_m row read once); the attention kernels read Q / K (and write dQ /
+  // dK) through ld = ncat_m H; the dZ GEMM is then one K = ncat_m H source.  Columns in pair order, a
+  // pair's Q before its K.  Opt-in (MMF_QK_CAT=1): measured at C5 it is slower -- 13.05 / 13.35 ms
+  // against 12.62 / 12.62 (profiles/r05/c5_qk_cat/): the 2 560-column GEMM on the LDS-DMA kernel
+  // (1.75 ms) loses to the weight-stationary per-pair GEMMs (1.46 ms), and the attention kernels'
+  // head-slice rows 5 KB apart instead of 512 B cost them 2-3 %.
+  p.qk_cat = p.qk_gemm_b16 && switch_set<SW_QK_CAT>();
+  for (int g = 0; g < np; ++g) {
+    p.qcol[g] = p.kcol[g] = -1;
+    if (!p.qk_cat || !p.attn(g)) continue;
+    p.qcol[g] = p.ncat[d->pair_q[g]]++;
+    p.kcol[g] = p.ncat[d->pair_k[g]]++;
+  }
+
+  // The backward on bf16 dQ / dK ("medium", every pair a bf16 Q/K pair of the one-pass kernels):
+  // attn_poolL_bwd_fused_bf16 stores dQ / dK as bf16 -- the rounding their GEMM consumers' MFMA
+  // operands get anyway -- and the dZ GEMM (dQ W_q + dK W_k, RK x KR on the forward's W_q / W_k
+  // copies) and the pairs' weight gradients (dQ^T P_q, dK^T P_k: KR x KR on the P_m copies) run the
+  // LDS-DMA kernel's bf16-operand forms: half the bytes written by the attention backward and read
+  // by both GEMMs.  The value-path term E_m is then materialised (pool_e) instead of riding in the
+  // dZ GEMM as K = heads sources.  MMF_NO_DQK_B16=1: fp32 dQ / dK (A/B).
+  p.dqk_b16 = d->training && p.qk_gemm_b16 && !switch_set<SW_NO_DQK_B16>() && nb16 == np;
+
+  // The modality projections on bf16 operands ("medium", dqk_b16): the input-mask kernel stores
+  // X'_m as bf16 (the rounding the fp32-operand GEMM gave its MFMA operands in-kernel) and W_proj is
+  // converted with the W_q / W_k copies, so the projection GEMM, its weight gradient (dZ^T X') and
+  // dX = dZ W run the LDS-DMA kernel's bf16 forms (RK x RK, KR x KR, RK x KR); the dZ GEMM stores dZ
+  // as bf16.  Half the bytes of X' (written once, read twice) and dZ (written once, read twice).
+  // The projection bias gradient is then the column sum of the bf16 dZ, as the Q / K ones are of
+  // the bf16 dQ / dK.  MMF_NO_PROJ_B16=1: the fp32-operand forms (A/B).
+  p.proj_b16 = p.dqk_b16 && !p.qk_cat && !switch_set<SW_NO_PROJ_B16>() && M + 2 * np <= CVT_MAX && H % 8 == 0;
+  for (int m = 0; m < M; ++m)
+    if (d->in_dim[m] % 8 != 0) p.proj_b16 = false;
+  // (proj_b16: the dZ GEMM takes the sign of P_m from its bf16 copy -- half the gate bytes;
+  // MMF_NO_GATE_B16=1 A/B)
+  p.gate_b16 = p.proj_b16 && !switch_set<SW_NO_GATE_B16>();
+  // dX_m chained into its dZ_m job's launch (fp32-operand forms).  Opt-in (MMF_DX_CHAIN=1):
+  // measured at C2 it saves nothing -- the chained kernel took 192.2 us
+  // for what the two launches take in 191.1 (profiles/r06/dx_chain/): every workgroup still runs
+  // dZ's epilogue, then dX's prologue, main loop and epilogue in lockstep with all the others, so
+  // the chain removes only the launch boundary and dZ's HBM re-read, neither of which bounds it
+  p.dx_chain = !p.dqk_b16 && !p.proj_b16 && switch_set<SW_DX_CHAIN>();
+
+  const bool no_pcol = switch_set<SW_NO_PCOL>(), no_poole = switch_set<SW_NO_POOLE>();
+  for (int m = 0; m < M; ++m) {
+    // The head (tail or generic) takes mean_L P_m from per-tile column sums written by the
+    // projection GEMM's epilogue when every 128-row tile lies inside one sample (pooled plan):
+    // L / 128 rows per sample instead of L (C5: the generic head read 400 MB with one
+    // workgroup per sample, 0.35 ms).
+    p.pcol_in_proj[m] = np && p.pool && Lm(d, m) % 128 == 0 && !no_pcol;
+    // dZ_m takes its value-path term E_m as extra K = heads sources of the dZ GEMM
+    // (pbarT against the per-sample dU) when a 128-row tile never straddles two
+    // samples and the pbarT rows are float4-able; otherwise pool_e materialises E_m.
+    p.poole_in_dz[m] = p.pool && !no_poole && !p.dqk_b16 && Lm(d, m) % 128 == 0 && H % 4 == 0 && nh % 4 == 0;
+  }
+
+  // Launch-lean single-key step (l1.hip): every modality 2-D (L = 1, the reference's own
+  // semantics), every ordered pair present, fp32 ("highest"), H, D_m <= 128 (% 4),
+  // C <= 16, float4-able inputs and weights.  It writes the single-key pooled plan's Saved / Ws
+  // slots (Ob = O = P' V, Ab = A, dOb = dV, dU = dP_k|g), so both plans size the buffers alike; the
+  // choice depends only on the descriptor and the pointers forward and backward both receive.
+  // MMF_NO_L1_LEAN=1: the general single-key plan (A/B).
+  // This is the descriptor half; the other half (lean_l1): 16-B aligned inputs and weights.
+  p.lean_l1 = !switch_set<SW_NO_L1_LEAN>() && d->matmul_precision == MMF_PRECISION_HIGHEST && M >= 2 &&
+              M <= L1_MAXM && np == M * (M - 1) && H % 4 == 0 && H <= L1_MAXH && nh <= 8 &&
+              d->num_classes <= L1_MAXC;
+  if (p.lean_l1) {
+    unsigned seen = 0;
+    for (int g = 0; g < np; ++g) seen |= 1u << (d->pair_q[g] * L1_MAXM + d->pair_k[g]);
+    if (__builtin_popcount(seen) != np) p.lean_l1 = false;
+  }
+  // l1_full: the C2 shape of the L = 1 kernels (l1.hip l1_full): H and every input width 128
+  p.l1_full = H == 128;
+  for (int m = 0; m < M; ++m) {
+    if (Lm(d, m) != 1 || d->in_dim[m] % 4 != 0 || d->in_dim[m] > L1_MAXD) p.lean_l1 = false;
+    if (d->in_dim[m] != 128) p.l1_full = false;
+  }
+
+  // (MMF_WGRAD_SPLIT_CAP=n: at most n slabs per weight gradient, plan_wgrads)
+  if (const char* e = switch_value<SW_WGRAD_SPLIT_CAP>()) p.split_cap = std::max(1, atoi(e));
+
+  // The keep words are drawn on a side stream (attn_keep_words_kernel) while the projection GEMMs
+  // run, so the attention forward reads them instead of drawing inline: pooled plan, training, with
+  // long-key pairs (C5: the draws are a third of the one-pass forward's VALU work; at C2's 128 keys
+  // the concurrent draws slow the fp32 GEMMs more than the lean forward gains, 0.979 -> 0.986 ms).
+  // MMF_NO_SIDE_STREAM=1: inline (A/B); MMF_SIDE_STREAM=1: also without long pairs.
+  // MMF_KW_SERIAL=1 (A/B): the draws on the call's stream, ahead of the projection GEMM.  At C2 the
+  // lean forward drops 112-116 -> 90 us but the draw kernel takes 26.5 us: 0.968 -> 0.971-0.975 ms
+  // (DESIGN §9).
+  // Without long-key pairs (and at most 16 pairs) the draws are made by extra workgroups of the
+  // input-mask kernel, interleaved with its HBM-bound rows: at C2 the lean forward drops
+  // 113 -> 91 us and the mask kernel grows 23 -> 41 us, step 0.969 -> 0.960 ms median
+  // (DESIGN §7).  MMF_NO_KW_FUSED=1: off; MMF_KW_FUSED=1: also with long-key pairs.
+  p.keep_words = KeepWords::INLINE;
+  if (p.drop && p.pool && nattn && !switch_set<SW_NO_SIDE_STREAM>()) {
+    const bool side = switch_set<SW_SIDE_STREAM>(), serial = switch_set<SW_KW_SERIAL>();
+    const bool fold_forced = switch_set<SW_KW_FUSED>();
+    bool fold = !side && !serial && !switch_set<SW_NO_KW_FUSED>() && (!attn_long || fold_forced);
+    if (fold) {
+      // at most 16 pairs, each under launch_mask_dropout's 2^31-word bound: otherwise the
+      // side-stream / inline draws (never a failed forward)
+      int nkw = 0;
+      for (int g = 0; g < np && fold; ++g) {
+        const int lq = Lm(d, d->pair_q[g]), lk = Lm(d, d->pair_k[g]);
+        if (!p.attn(g) || !kw_foldable(lk)) continue;
+        if (nkw++ == 16 || (int64_t)d->batch * nh * lq * (lk / 32) >= ((int64_t)1 << 31)) fold = false;
+      }
+      p.kw_fold_unfit = !fold && fold_forced;
+    }
+    if (fold) p.keep_words = KeepWords::MASK_FOLD;
+    else if (serial) p.keep_words = KeepWords::SERIAL;
+    else if (attn_long || side) p.keep_words = KeepWords::SIDE_STREAM;
+  }
+  return p;
 }
 
 // Before any launch: the plan switches are the ones the caller sized its buffers under, and the
 // layout this call computed fits the capacities the caller declared (need_* = the Bump offsets;
 // ~0 = that buffer is not used by the call).
-int check_buffers(const mmf_hybrid_desc* d, size_t need_saved, size_t need_ws) {
-  const uint32_t now = plan_flags_now();
+int check_buffers(const HybridPlan& plan, const mmf_hybrid_desc* d, size_t need_saved, size_t need_ws) {
+  const uint32_t now = plan.flags;
   if (d->plan_flags != now)
     return fail(MMF_EINVAL,
                 "the plan switches (MMF_* environment) changed since this descriptor's buffers were sized "
@@ -71,153 +268,6 @@ int check_buffers(const mmf_hybrid_desc* d, size_t need_saved, size_t need_ws) {
     return fail(MMF_EINVAL, "workspace too small: this call's layout needs %zu bytes, workspace_capacity is %llu",
                 need_ws, (unsigned long long)d->workspace_capacity);
   return MMF_OK;
-}
-
-inline int Lm(const mmf_hybrid_desc* d, int m) { return d->seq_len[m] > 0 ? d->seq_len[m] : 1; }
-inline bool dropping(const mmf_hybrid_desc* d) { return d->training && d->dropout > 0.f; }
-// Pair g attends over ONE key (2-D inputs, the reference's own case, or a 3-D key of
-// length 1): softmax over one key is the mask indicator, so the pair has no Q / K /
-// QK^T work and its query_proj / key_proj gradients are exactly zero (single_key.hip).
-inline bool single_key(const mmf_hybrid_desc* d, int g) { return Lm(d, d->pair_k[g]) == 1; }
-// head_dim beyond the fused attention kernels' register budget (MMF_MAX_HEAD_DIM): the pair's
-// scores are materialised and contracted by GEMMs (wide.hip)
-inline bool wide_pair(const mmf_hybrid_desc* d, int g) {
-  return !single_key(d, g) && d->hidden / d->num_heads > MMF_MAX_HEAD_DIM;
-}
-
-// Pooled plan (attention.hip "Pooled-output attention"): keys up to 128 run the
-// one-chunk kernels, longer keys the streamed long-key kernels; the pooled
-// helpers keep heads x Lk query-mean probabilities in LDS (pool.hip POOL_PB_CAP).
-bool use_pool(const mmf_hybrid_desc* d) {
-  if (d->num_heads > 8) return false;
-  for (int g = 0; g < d->num_pairs; ++g)
-    if (Lm(d, d->pair_k[g]) * d->num_heads > POOL_PB_CAP) return false;
-  return true;
-}
-inline int kw_ld(int lk) { return lk <= 128 ? 4 : (lk + 31) / 32; }
-inline bool long_keys(const mmf_hybrid_desc* d) {
-  for (int g = 0; g < d->num_pairs; ++g)
-    if (Lm(d, d->pair_k[g]) > 128) return true;
-  return false;
-}
-
-bool use_tail(const mmf_hybrid_desc* d);
-
-// Training forward keeps the pre-dropout probabilities for the fused backward (no S recompute
-// there): the pooled plan with every attention-kernel pair inside the lean fused kernels' shape
-// (attn_pstore_ok).  All pairs or none (one launch each way).  Opt-in (MMF_PSTORE=1): measured
-// at C2 it costs more than it saves (the 402 MB blob's write and read slow the
-// neighbouring kernels more than the skipped recompute gains).
-bool pstore_on(const mmf_hybrid_desc* d) {
-  if (!d->training || !use_pool(d) || !getenv("MMF_PSTORE")) return false;
-  const int hd = d->hidden / d->num_heads;
-  int n = 0;
-  for (int g = 0; g < d->num_pairs; ++g) {
-    if (single_key(d, g) || wide_pair(d, g)) continue;
-    if (!attn_pstore_ok(Lm(d, d->pair_q[g]), Lm(d, d->pair_k[g]), 1, hd) || d->hidden % 4 != 0) return false;
-    ++n;
-  }
-  return n > 0;
-}
-
-// "medium" long-key pairs on the one-pass kernels (attn_long.hip) keep Q and K in bf16: the
-// Q/K GEMM rounds its output once (EPI_BF16) -- exactly the rounding the kernels applied when
-// they loaded fp32 rows -- so the GEMM writes and the attention kernels read half the bytes.
-// All long pairs or none (the one-pass launches take every long pair); off with
-// return_attention (the attention-map kernels read fp32 Q / K) and whenever the streamed
-// kernels could run (MMF_NO_LONG_FUSED, MMF_NO_FUSED_BWD; MMF_NO_BF16_QK: fp32 Q / K, A/B).
-bool qk_bf16_on(const mmf_hybrid_desc* d) {
-  if (math_mode() != 1 || !use_pool(d) || d->return_attention || getenv("MMF_NO_LONG_FUSED") ||
-      getenv("MMF_NO_FUSED_BWD") || getenv("MMF_NO_BF16_QK"))
-    return false;
-  const int hd = d->hidden / d->num_heads;
-  if (hd > 64 || hd % 8 != 0 || d->hidden % 8 != 0) return false;
-  int n = 0;
-  for (int g = 0; g < d->num_pairs; ++g) {
-    if (single_key(d, g) || wide_pair(d, g)) continue;
-    const int lk = Lm(d, d->pair_k[g]);
-    if (lk <= 128) continue;
-    if (lk > 512 || lk % 32 != 0) return false;
-    ++n;
-  }
-  return n > 0;
-}
-bool pair_qk_bf16(const mmf_hybrid_desc* d, int g) {
-  return !single_key(d, g) && !wide_pair(d, g) && Lm(d, d->pair_k[g]) > 128 && qk_bf16_on(d);
-}
-
-// The Q/K projection GEMM on bf16 copies of both operands ("medium", every Q/K pair stores bf16
-// Q / K): the projection GEMM's epilogue also writes P_m as bf16 (EPI_BF16COPY) and the pairs'
-// W_q / W_k are converted once per forward; the GEMM (launch_gemm_b16) then streams half the
-// operand bytes and feeds its MFMAs without conversions.  MMF_NO_GEMM_B16=1: the fp32-operand form.
-bool qk_gemm_b16(const mmf_hybrid_desc* d) {
-  if (math_mode() != 1 || getenv("MMF_NO_GEMM_B16") || d->hidden % 8 != 0) return false;
-  int n = 0;
-  for (int g = 0; g < d->num_pairs; ++g) {
-    if (single_key(d, g) || wide_pair(d, g)) continue;
-    if (!pair_qk_bf16(d, g)) return false;
-    ++n;
-  }
-  return n > 0 && 2 * n <= CVT_MAX;
-}
-
-// The Q / K projections concatenated per modality ("medium", qk_gemm_b16): modality m's Q (pairs
-// with query m) and K (pairs with key m) are column blocks of one (B L_m) x (ncat_m H) bf16 matrix,
-// written by ONE bf16 GEMM of P_m against the stacked W_q / W_k copies (C5: 6 GEMMs of N = 2 560 in
-// place of 60 of N = 256, each P_m row read once); the attention kernels read Q / K (and write dQ /
-// dK) through ld = ncat_m H; the dZ GEMM is then one K = ncat_m H source.  Columns in pair order, a
-// pair's Q before its K.  Opt-in (MMF_QK_CAT=1): measured at C5 it is slower -- 13.05 / 13.35 ms
-// against 12.62 / 12.62 (profiles/r05/c5_qk_cat/): the 2 560-column GEMM on the LDS-DMA kernel
-// (1.75 ms) loses to the weight-stationary per-pair GEMMs (1.46 ms), and the attention kernels'
-// head-slice rows 5 KB apart instead of 512 B cost them 2-3 %.
-bool qk_cat_on(const mmf_hybrid_desc* d) { return qk_gemm_b16(d) && getenv("MMF_QK_CAT"); }
-void qk_cols(const mmf_hybrid_desc* d, int* qcol, int* kcol, int* ncat) {
-  for (int m = 0; m < d->num_modalities; ++m) ncat[m] = 0;
-  for (int g = 0; g < d->num_pairs; ++g) {
-    qcol[g] = kcol[g] = -1;
-    if (single_key(d, g) || wide_pair(d, g)) continue;
-    qcol[g] = ncat[d->pair_q[g]]++;
-    kcol[g] = ncat[d->pair_k[g]]++;
-  }
-}
-
-// The backward on bf16 dQ / dK ("medium", every pair a bf16 Q/K pair of the one-pass kernels):
-// attn_poolL_bwd_fused_bf16 stores dQ / dK as bf16 -- the rounding their GEMM consumers' MFMA
-// operands get anyway -- and the dZ GEMM (dQ W_q + dK W_k, RK x KR on the forward's W_q / W_k
-// copies) and the pairs' weight gradients (dQ^T P_q, dK^T P_k: KR x KR on the P_m copies) run the
-// LDS-DMA kernel's bf16-operand forms: half the bytes written by the attention backward and read
-// by both GEMMs.  The value-path term E_m is then materialised (pool_e) instead of riding in the
-// dZ GEMM as K = heads sources.  MMF_NO_DQK_B16=1: fp32 dQ / dK (A/B).
-bool dqk_b16_on(const mmf_hybrid_desc* d) {
-  if (!d->training || !qk_gemm_b16(d) || getenv("MMF_NO_DQK_B16")) return false;
-  for (int g = 0; g < d->num_pairs; ++g)
-    if (!pair_qk_bf16(d, g)) return false;
-  return d->num_pairs > 0;
-}
-
-// The modality projections on bf16 operands ("medium", dqk_b16_on): the input-mask kernel stores
-// X'_m as bf16 (the rounding the fp32-operand GEMM gave its MFMA operands in-kernel) and W_proj is
-// converted with the W_q / W_k copies, so the projection GEMM, its weight gradient (dZ^T X') and
-// dX = dZ W run the LDS-DMA kernel's bf16 forms (RK x RK, KR x KR, RK x KR); the dZ GEMM stores dZ
-// as bf16.  Half the bytes of X' (written once, read twice) and dZ (written once, read twice).
-// The projection bias gradient is then the column sum of the bf16 dZ, as the Q / K ones are of
-// the bf16 dQ / dK.  MMF_NO_PROJ_B16=1: the fp32-operand forms (A/B).
-bool proj_b16_on(const mmf_hybrid_desc* d) {
-  if (!dqk_b16_on(d) || qk_cat_on(d) || getenv("MMF_NO_PROJ_B16")) return false;
-  int n = 0;
-  for (int g = 0; g < d->num_pairs; ++g) n += 2;
-  if (d->num_modalities + n > CVT_MAX) return false;
-  for (int m = 0; m < d->num_modalities; ++m)
-    if (d->in_dim[m] % 8 != 0) return false;
-  return d->hidden % 8 == 0;
-}
-
-// The head (tail or generic) takes mean_L P_m from per-tile column sums written by the
-// projection GEMM's epilogue when every 128-row tile lies inside one sample (pooled plan):
-// L / 128 rows per sample instead of L (C5: the generic head read 400 MB with one
-// workgroup per sample, 0.35 ms).
-bool pcol_in_proj(const mmf_hybrid_desc* d, int m) {
-  return d->num_pairs && use_pool(d) && Lm(d, m) % 128 == 0 && !getenv("MMF_NO_PCOL");
 }
 
 struct Saved {
@@ -233,40 +283,37 @@ struct Saved {
   float* pbarT[MMF_MAX_PAIRS];   // (B, Lk, heads): pbar as the RK operand of the dZ GEMM's E_m term
   uint32_t* bits[MMF_MAX_PAIRS];
   float *Pw[MMF_MAX_PAIRS], *Pdw[MMF_MAX_PAIRS];   // wide pairs: probabilities, post-dropout (general)
-  float* pst[MMF_MAX_PAIRS];                        // stored probabilities (pstore_on)
+  float* pst[MMF_MAX_PAIRS];                        // stored probabilities (pstore)
   float *pooled, *scores, *weights, *fused, *h1;
   __bf16* Pb[MMF_MAX_MODALITIES];                  // bf16 copies of P_m (qk_gemm_b16)
   __bf16 *Wqb[MMF_MAX_PAIRS], *Wkb[MMF_MAX_PAIRS];  // bf16 copies of W_q / W_k (qk_gemm_b16)
-  __bf16* Wpb[MMF_MAX_MODALITIES];                 // bf16 copies of W_proj (proj_b16_on; Xd is then bf16)
-  int32_t ldq[MMF_MAX_PAIRS], ldk[MMF_MAX_PAIRS];   // elements between Q (K) rows: H, or ncat H (qk_cat_on)
-  // qk_cat_on: per modality the Q / K block matrix, the stacked W copies (Wqb / Wkb point into
-  // them), the stacked biases, the column count; per pair its Q / K column slots
+  __bf16* Wpb[MMF_MAX_MODALITIES];                 // bf16 copies of W_proj (proj_b16; Xd is then bf16)
+  int32_t ldq[MMF_MAX_PAIRS], ldk[MMF_MAX_PAIRS];   // elements between Q (K) rows: H, or ncat H (qk_cat)
+  // qk_cat: per modality the Q / K block matrix, the stacked W copies (Wqb / Wkb point into
+  // them), the stacked biases (the column slots: HybridPlan::qcol / kcol / ncat)
   __bf16* QKc[MMF_MAX_MODALITIES];
   __bf16* Wc[MMF_MAX_MODALITIES];
   float* bc[MMF_MAX_MODALITIES];
-  int32_t ncat[MMF_MAX_MODALITIES];
-  int32_t qcol[MMF_MAX_PAIRS], kcol[MMF_MAX_PAIRS];
 };
 
-void layout_saved(const mmf_hybrid_desc* d, Bump& bp, Saved& s) {
+void layout_saved(const HybridPlan& plan, const mmf_hybrid_desc* d, Bump& bp, Saved& s) {
   memset(&s, 0, sizeof(s));
   const size_t B = d->batch, H = d->hidden, M = d->num_modalities, nh = d->num_heads;
-  const bool pool = use_pool(d);
-  const bool cat = qk_cat_on(d);
-  if (cat) qk_cols(d, s.qcol, s.kcol, s.ncat);
+  const bool pool = plan.pool;
+  const bool cat = plan.qk_cat;
   for (int g = 0; g < d->num_pairs; ++g) s.ldq[g] = s.ldk[g] = (int32_t)H;
   s.rng = bp.take<RngSnap>(1);
-  const bool pb16 = proj_b16_on(d);
+  const bool pb16 = plan.proj_b16;
   for (int m = 0; m < d->num_modalities; ++m)
     s.Xd[m] = pb16 ? reinterpret_cast<float*>(bp.take<__bf16>(B * Lm(d, m) * d->in_dim[m]))
                    : bp.take<float>(B * Lm(d, m) * d->in_dim[m]);
   for (int m = 0; m < d->num_modalities && pb16; ++m) s.Wpb[m] = bp.take<__bf16>(H * d->in_dim[m]);
   for (int m = 0; m < d->num_modalities; ++m) s.P[m] = bp.take<float>(B * Lm(d, m) * H);
   for (int m = 0; m < d->num_modalities; ++m)
-    if (pcol_in_proj(d, m)) s.Pcol[m] = bp.take<float>(B * (Lm(d, m) / 128) * H);
+    if (plan.pcol_in_proj[m]) s.Pcol[m] = bp.take<float>(B * (Lm(d, m) / 128) * H);
   for (int g = 0; g < d->num_pairs; ++g) {
     const size_t lq = Lm(d, d->pair_q[g]), lk = Lm(d, d->pair_k[g]);
-    const bool sk = single_key(d, g), wide = wide_pair(d, g);
+    const bool sk = plan.sk(g), wide = plan.wide(g);
     if (!sk) {
       if (!cat) {
         s.Q[g] = bp.take<float>(B * lq * H);
@@ -285,8 +332,8 @@ void layout_saved(const mmf_hybrid_desc* d, Bump& bp, Saved& s) {
       s.r[g] = bp.take<float>(B * nh);
       s.Ob[g] = bp.take<float>(B * H);
       s.Ab[g] = bp.take<float>(B * H);
-      if (dropping(d) && !sk && !wide) s.bits[g] = bp.take<uint32_t>(B * nh * lq * kw_ld((int)lk));
-      if (!sk && !wide && pstore_on(d)) s.pst[g] = bp.take<float>(B * nh * attn_pstore_floats((int)lq));
+      if (plan.drop && !sk && !wide) s.bits[g] = bp.take<uint32_t>(B * nh * lq * kw_ld((int)lk));
+      if (!sk && !wide && plan.pstore) s.pst[g] = bp.take<float>(B * nh * attn_pstore_floats((int)lq));
     } else {
       s.V[g] = bp.take<float>(B * lk * H);
       s.O[g] = bp.take<float>(B * lq * H);
@@ -298,10 +345,10 @@ void layout_saved(const mmf_hybrid_desc* d, Bump& bp, Saved& s) {
   s.weights = bp.take<float>(B * M);
   s.fused = bp.take<float>(B * H);
   s.h1 = bp.take<float>(B * H);
-  if (qk_gemm_b16(d)) {
+  if (plan.qk_gemm_b16) {
     bool used[MMF_MAX_MODALITIES] = {};
     for (int g = 0; g < d->num_pairs; ++g)
-      if (!single_key(d, g) && !wide_pair(d, g)) {
+      if (!plan.sk(g) && !plan.wide(g)) {
         used[d->pair_q[g]] = used[d->pair_k[g]] = true;
         if (!cat) {
           s.Wqb[g] = bp.take<__bf16>(H * H);
@@ -313,20 +360,20 @@ void layout_saved(const mmf_hybrid_desc* d, Bump& bp, Saved& s) {
   }
   if (cat) {
     for (int m = 0; m < d->num_modalities; ++m)
-      if (s.ncat[m] > 0) {
-        s.QKc[m] = bp.take<__bf16>(B * Lm(d, m) * s.ncat[m] * H);
-        s.Wc[m] = bp.take<__bf16>((size_t)s.ncat[m] * H * H);
-        s.bc[m] = bp.take<float>((size_t)s.ncat[m] * H);
+      if (plan.ncat[m] > 0) {
+        s.QKc[m] = bp.take<__bf16>(B * Lm(d, m) * plan.ncat[m] * H);
+        s.Wc[m] = bp.take<__bf16>((size_t)plan.ncat[m] * H * H);
+        s.bc[m] = bp.take<float>((size_t)plan.ncat[m] * H);
       }
     for (int g = 0; g < d->num_pairs; ++g) {
-      if (s.qcol[g] < 0) continue;
+      if (plan.qcol[g] < 0) continue;
       const int q = d->pair_q[g], k = d->pair_k[g];
-      s.Q[g] = reinterpret_cast<float*>(s.QKc[q] + (size_t)s.qcol[g] * H);
-      s.K[g] = reinterpret_cast<float*>(s.QKc[k] + (size_t)s.kcol[g] * H);
-      s.ldq[g] = s.ncat[q] * (int32_t)H;
-      s.ldk[g] = s.ncat[k] * (int32_t)H;
-      s.Wqb[g] = s.Wc[q] + (size_t)s.qcol[g] * H * H;
-      s.Wkb[g] = s.Wc[k] + (size_t)s.kcol[g] * H * H;
+      s.Q[g] = reinterpret_cast<float*>(s.QKc[q] + (size_t)plan.qcol[g] * H);
+      s.K[g] = reinterpret_cast<float*>(s.QKc[k] + (size_t)plan.kcol[g] * H);
+      s.ldq[g] = plan.ncat[q] * (int32_t)H;
+      s.ldk[g] = plan.ncat[k] * (int32_t)H;
+      s.Wqb[g] = s.Wc[q] + (size_t)plan.qcol[g] * H * H;
+      s.Wkb[g] = s.Wc[k] + (size_t)plan.kcol[g] * H * H;
     }
   }
 }
@@ -339,32 +386,30 @@ struct Ws {
   float *dS[MMF_MAX_PAIRS], *dPd[MMF_MAX_PAIRS];                             // wide pairs
   float* E[MMF_MAX_MODALITIES];                                              // pooled
   float* dZ[MMF_MAX_MODALITIES];
-  // qk_cat_on: per modality the dQ / dK block matrix (the layout of Saved::QKc: fp32-sized, bf16
-  // when dqk_b16_on); dQ / dK point into it
+  // qk_cat: per modality the dQ / dK block matrix (the layout of Saved::QKc: fp32-sized, bf16
+  // when dqk_b16); dQ / dK point into it
   float* dQc[MMF_MAX_MODALITIES];
 };
 
-void layout_ws(const mmf_hybrid_desc* d, Bump& bp, Ws& w) {
+void layout_ws(const HybridPlan& plan, const mmf_hybrid_desc* d, Bump& bp, Ws& w) {
   memset(&w, 0, sizeof(w));
   const size_t B = d->batch, H = d->hidden, M = d->num_modalities, nh = d->num_heads;
-  const bool pool = use_pool(d);
-  const bool cat = qk_cat_on(d), b16 = dqk_b16_on(d);
-  int qcol[MMF_MAX_PAIRS], kcol[MMF_MAX_PAIRS], ncat[MMF_MAX_MODALITIES];
-  if (cat) qk_cols(d, qcol, kcol, ncat);
+  const bool pool = plan.pool;
+  const bool cat = plan.qk_cat, b16 = plan.dqk_b16;
   w.dz1 = bp.take<float>(B * H);
   w.dfused = bp.take<float>(B * H);
   w.cvec = bp.take<float>(B * M * H);
   w.dscore = bp.take<float>(B * M);
   for (int g = 0; g < d->num_pairs; ++g) {
     const size_t lq = Lm(d, d->pair_q[g]), lk = Lm(d, d->pair_k[g]);
-    if (!single_key(d, g)) {
+    if (!plan.sk(g)) {
       if (!cat) {
         w.dQ[g] = bp.take<float>(B * lq * H);
         w.dK[g] = bp.take<float>(B * lk * H);
       }
       w.dsum[g] = bp.take<float>(B * nh * lq);
     }
-    if (wide_pair(d, g)) {
+    if (plan.wide(g)) {
       w.dS[g] = bp.take<float>(B * nh * lq * lk);
       if (!pool) w.dPd[g] = bp.take<float>(B * nh * lq * lk);
     }
@@ -383,16 +428,16 @@ void layout_ws(const mmf_hybrid_desc* d, Bump& bp, Ws& w) {
   }
   if (cat) {
     for (int m = 0; m < d->num_modalities; ++m)
-      if (ncat[m] > 0) w.dQc[m] = bp.take<float>(B * Lm(d, m) * ncat[m] * H);
+      if (plan.ncat[m] > 0) w.dQc[m] = bp.take<float>(B * Lm(d, m) * plan.ncat[m] * H);
     // (element offsets of the column slots: bf16 or fp32 elements, as the attention backward writes)
     auto slot = [&](int m, int col) -> float* {
       return b16 ? reinterpret_cast<float*>(reinterpret_cast<__bf16*>(w.dQc[m]) + (size_t)col * H)
                  : w.dQc[m] + (size_t)col * H;
     };
     for (int g = 0; g < d->num_pairs; ++g) {
-      if (qcol[g] < 0) continue;
-      w.dQ[g] = slot(d->pair_q[g], qcol[g]);
-      w.dK[g] = slot(d->pair_k[g], kcol[g]);
+      if (plan.qcol[g] < 0) continue;
+      w.dQ[g] = slot(d->pair_q[g], plan.qcol[g]);
+      w.dK[g] = slot(d->pair_k[g], plan.kcol[g]);
     }
   }
 }
@@ -426,7 +471,8 @@ int check_hybrid(const mmf_hybrid_desc* d) {
   if (!(d->dropout >= 0.f && d->dropout < 1.f))
     return fail(MMF_EINVAL, "dropout must be in [0, 1) (got %g)", (double)d->dropout);
   for (int g = 0; g < d->num_pairs; ++g)
-    if (wide_pair(d, g) && !wide_supported(d->batch, d->num_heads, Lm(d, d->pair_q[g]), Lm(d, d->pair_k[g])))
+    if (pair_kind(Lm(d, d->pair_k[g]), d->hidden / d->num_heads) == PAIR_WIDE &&
+        !wide_supported(d->batch, d->num_heads, Lm(d, d->pair_q[g]), Lm(d, d->pair_k[g])))
       return fail(MMF_ELIMIT, "head_dim %d: pair %d's (heads x Lq x Lk) score tensor is too large",
                   d->hidden / d->num_heads, g);
   return MMF_OK;
@@ -437,13 +483,13 @@ int check_hybrid(const mmf_hybrid_desc* d) {
 // part (mmf_hybrid_train_step_part): 0 every weight, 1 every weight but the modality projections'
 // (known once the attention backward has run), 2 the projections' alone (after dZ); the split
 // counts are sized for the launch the part makes.
-void plan_wgrads(const mmf_hybrid_desc* d, const float* const* x, const float* mask,
+void plan_wgrads(const HybridPlan& plan, const mmf_hybrid_desc* d, const float* const* x, const float* mask,
                  const float* dlogits, const Saved& s, const Ws& w, const mmf_hybrid_grads* G,
                  Bump& bw, WgradPlan& wp, int part = 0) {
   const bool want_pairs = part != 2, want_proj = part != 1;
   const int B = d->batch, M = d->num_modalities, H = d->hidden, C = d->num_classes;
   const int nh = d->num_heads, hd = H / nh;
-  const bool pool = use_pool(d);
+  const bool pool = plan.pool;
   static const mmf_hybrid_grads kNull = {};
   const mmf_hybrid_grads* g = G ? G : &kNull;
   // Split counts of the long (B*L-row) contractions, sized per launch: launch_gemm packs
@@ -456,7 +502,7 @@ void plan_wgrads(const mmf_hybrid_desc* d, const float* const* x, const float* m
   for (int p = 0; p < d->num_pairs && want_pairs; ++p) {
     const int lq = Lm(d, d->pair_q[p]), lk = Lm(d, d->pair_k[p]);
     if (!pool) nbig += (B * lq >= kBigRows) + (B * lk >= kBigRows);
-    if (!single_key(d, p)) nbig += (B * lq >= kBigRows) + (B * lk >= kBigRows);
+    if (!plan.sk(p)) nbig += (B * lq >= kBigRows) + (B * lk >= kBigRows);
   }
   for (int m = 0; m < M && want_proj; ++m) nbig += (B * Lm(d, m) >= kBigRows);
   const int slots = 3 * device_cu_count();
@@ -466,7 +512,7 @@ void plan_wgrads(const mmf_hybrid_desc* d, const float* const* x, const float* m
     if (rows < kBigRows) return 0;
     const int per = bi++ < nfull ? GEMM_MAX_GROUPS : rem;
     int sp = slots / per;
-    if (const char* e = getenv("MMF_WGRAD_SPLIT_CAP")) sp = std::min(sp, std::max(1, atoi(e)));
+    if (plan.split_cap) sp = std::min(sp, plan.split_cap);
     return std::max(1, std::min(sp, 256));
   };
   if (want_pairs) {
@@ -497,13 +543,13 @@ void plan_wgrads(const mmf_hybrid_desc* d, const float* const* x, const float* m
       wp.split_hint = hint(B * lk);
       plan_wgrad(wp, bw, H, H, B * lk, opnd(w.dV[p], H), opnd(s.P[k], H), g->v[p].w, g->v[p].b);
     }
-    if (single_key(d, p)) {
+    if (plan.sk(p)) {
       // softmax over one key: no gradient reaches query_proj / key_proj (exact zeros)
       plan_zero(wp, H, H, g->q[p].w, g->q[p].b);
       plan_zero(wp, H, H, g->k[p].w, g->k[p].b);
       continue;
     }
-    const bool b16 = dqk_b16_on(d);
+    const bool b16 = plan.dqk_b16;
     // (bf16: dQ / dK and the P_m copies as __bf16 addresses, launch_gemm_b16's KR x KR form)
     const float* pq = b16 ? reinterpret_cast<const float*>(s.Pb[q]) : s.P[q];
     const float* pk = b16 ? reinterpret_cast<const float*>(s.Pb[k]) : s.P[k];
@@ -519,44 +565,30 @@ void plan_wgrads(const mmf_hybrid_desc* d, const float* const* x, const float* m
     const int L = Lm(d, m), D = d->in_dim[m];
     wp.split_hint = hint(B * L);
     plan_wgrad(wp, bw, H, D, B * L, opnd(w.dZ[m], H), opnd(s.Xd[m], D), g->proj[m].w, g->proj[m].b);
-    // (proj_b16_on: dZ and X' are bf16, launch_gemm_b16's KR x KR form)
-    if (proj_b16_on(d) && !wp.size_only) { wp.jobs_b16.push_back(wp.jobs.back()); wp.jobs.pop_back(); }
+    // (proj_b16: dZ and X' are bf16, launch_gemm_b16's KR x KR form)
+    if (plan.proj_b16 && !wp.size_only) { wp.jobs_b16.push_back(wp.jobs.back()); wp.jobs.pop_back(); }
     wp.split_hint = 0;
   }
 }
 
-size_t saved_bytes(const mmf_hybrid_desc* d) {
-  MathScope math_(d->matmul_precision);   // (the layout depends on the precision: qk_gemm_b16)
-  Bump bp(nullptr);
-  Saved s{};
-  layout_saved(d, bp, s);
-  return bp.off + 256;
-}
-
-size_t workspace_bytes(const mmf_hybrid_desc* d) {
-  MathScope math_(d->matmul_precision);
-  Bump bs(nullptr);
-  Saved s{};
-  layout_saved(d, bs, s);
-  Bump bw(nullptr);
-  Ws w;
-  layout_ws(d, bw, w);
-  // the largest slab area of a one-launch backward and of its two parts (their slabs share the
-  // area: part 1's reduce has run before part 2's slabs are written)
+// The workspace a laid-out call needs past its Ws slots (bw: the Bump after layout_ws): the largest
+// slab area of a one-launch backward and of its two parts (their slabs share the area: part 1's
+// reduce has run before part 2's slabs are written)
+size_t wgrads_top(const HybridPlan& plan, const mmf_hybrid_desc* d, const Saved& s, const Ws& w, const Bump& bw) {
   size_t top = 0;
   for (int part = 0; part < 3; ++part) {
     Bump b = bw;
     WgradPlan wp;
     wp.size_only = true;
-    plan_wgrads(d, nullptr, nullptr, nullptr, s, w, nullptr, b, wp, part);
+    plan_wgrads(plan, d, nullptr, nullptr, nullptr, s, w, nullptr, b, wp, part);
     top = std::max(top, b.off);
   }
-  return top + 256;
+  return top;
 }
 
-void fill_head(HeadArgs& ha, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* mask,
+void fill_head(HeadArgs& ha, const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* mask,
                const Saved& s) {
-  const bool pool = use_pool(d);
+  const bool pool = plan.pool;
   memset(&ha, 0, sizeof(ha));
   ha.B = d->batch; ha.M = d->num_modalities; ha.H = d->hidden; ha.mask = mask;
   ha.scale_by_mask = 1;
@@ -583,12 +615,7 @@ void fill_head(HeadArgs& ha, const mmf_hybrid_desc* d, const mmf_hybrid_params* 
   ha.pooled = s.pooled; ha.scores = s.scores; ha.weights = s.weights; ha.fused = s.fused;
 }
 
-bool use_tail(const mmf_hybrid_desc* d) {
-  return use_pool(d) && !long_keys(d) && tail_supported(d->num_modalities, d->hidden, d->num_classes, d->num_heads,
-                                       d->hidden / d->num_heads, d->num_pairs);
-}
-
-void fill_tail(TailArgs& ta, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* mask,
+void fill_tail(TailArgs& ta, const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* mask,
                const Saved& s) {
   memset(&ta, 0, sizeof(ta));
   const int M = d->num_modalities;
@@ -618,13 +645,13 @@ void fill_tail(TailArgs& ta, const mmf_hybrid_desc* d, const mmf_hybrid_params* 
   for (int m = 0; m < M; ++m) ta.inv_cnt[m] = 1.0f / (float)cnt[m];
   ta.W1 = W->cls1.w; ta.b1 = W->cls1.b; ta.W2 = W->cls2.w; ta.b2 = W->cls2.b;
   ta.pooled = s.pooled; ta.scores = s.scores; ta.weights = s.weights; ta.fused = s.fused; ta.h1 = s.h1;
-  ta.drop_p = dropping(d) ? d->dropout : 0.f;
+  ta.drop_p = plan.drop ? d->dropout : 0.f;
   ta.drop_site = SITE_CLS;
   ta.rng = s.rng;
-  ta.gscale = dropping(d) ? 1.f / (1.f - d->dropout) : 1.f;
+  ta.gscale = plan.drop ? 1.f / (1.f - d->dropout) : 1.f;
 }
 
-AttnPair make_pair(const mmf_hybrid_desc* d, const Saved& s, const float* mask, int g) {
+AttnPair make_pair(const HybridPlan& plan, const mmf_hybrid_desc* d, const Saved& s, const float* mask, int g) {
   AttnPair a;
   memset(&a, 0, sizeof(a));
   const int q = d->pair_q[g], k = d->pair_k[g];
@@ -640,8 +667,8 @@ AttnPair make_pair(const mmf_hybrid_desc* d, const Saved& s, const float* mask, 
   a.keep_bits = s.bits[g];
   a.kw_ld = kw_ld(a.Lk);
   a.pstore = s.pst[g];
-  a.qk_bf16 = pair_qk_bf16(d, g) ? 1 : 0;
-  a.dqk_bf16 = a.qk_bf16 && dqk_b16_on(d) ? 1 : 0;
+  a.qk_bf16 = plan.pair_qk_bf16[g] ? 1 : 0;
+  a.dqk_bf16 = a.qk_bf16 && plan.dqk_b16 ? 1 : 0;
   return a;
 }
 
@@ -674,30 +701,11 @@ SkPair make_sk(const mmf_hybrid_desc* d, const Saved& s, const float* mask, int 
   return a;
 }
 
-// Launch-lean single-key step (l1.hip): every modality 2-D (L = 1, the reference's own
-// semantics), every ordered pair present, fp32 ("highest"), H, D_m <= 128 (% 4),
-// C <= 16, float4-able inputs and weights.  It writes the single-key pooled plan's Saved / Ws
-// slots (Ob = O = P' V, Ab = A, dOb = dV, dU = dP_k|g), so both plans size the buffers alike; the
-// choice depends only on the descriptor and the pointers forward and backward both receive.
-// MMF_NO_L1_LEAN=1: the general single-key plan (A/B).
-// the descriptor half of lean_l1 (the other half: 16-B aligned inputs and weights)
-bool lean_l1_desc(const mmf_hybrid_desc* d) {
-  const bool off = getenv("MMF_NO_L1_LEAN") != nullptr;
-  const int M = d->num_modalities, H = d->hidden;
-  if (off || d->matmul_precision != MMF_PRECISION_HIGHEST) return false;
-  if (M < 2 || M > L1_MAXM || d->num_pairs != M * (M - 1)) return false;
-  if (H % 4 != 0 || H > L1_MAXH || d->num_heads > 8 || d->num_classes > L1_MAXC) return false;
-  unsigned seen = 0;
-  for (int g = 0; g < d->num_pairs; ++g) seen |= 1u << (d->pair_q[g] * L1_MAXM + d->pair_k[g]);
-  if (__builtin_popcount(seen) != d->num_pairs) return false;
-  for (int m = 0; m < M; ++m)
-    if (Lm(d, m) != 1 || d->in_dim[m] % 4 != 0 || d->in_dim[m] > L1_MAXD) return false;
-  return true;
-}
-
-bool lean_l1(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x) {
+// The launch-lean L = 1 plan (HybridPlan::lean_l1, the descriptor's half) also needs 16-B aligned
+// inputs and weights
+bool lean_l1(const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x) {
   const int M = d->num_modalities;
-  if (!W || !x || !lean_l1_desc(d)) return false;
+  if (!W || !x || !plan.lean_l1) return false;
   for (int m = 0; m < M; ++m) {
     if (!aligned16(x[m]) || !aligned16(W->proj[m].w)) return false;
   }
@@ -706,22 +714,14 @@ bool lean_l1(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* 
   return aligned16(W->cls1.w);
 }
 
-// the C2 shape of the L = 1 kernels (l1.hip l1_full): H and every input width 128
-bool l1_desc_full(const mmf_hybrid_desc* d) {
-  if (d->hidden != 128) return false;
-  for (int m = 0; m < d->num_modalities; ++m)
-    if (d->in_dim[m] != 128) return false;
-  return true;
-}
-
-void fill_l1(L1Args& a, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
+void fill_l1(L1Args& a, const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
              const float* mask, const Saved& s) {
   memset(&a, 0, sizeof(a));
   const int M = d->num_modalities;
   a.B = d->batch; a.M = M; a.H = d->hidden; a.C = d->num_classes; a.heads = d->num_heads;
   a.npairs = d->num_pairs;
-  a.p = dropping(d) ? d->dropout : 0.f;
-  a.gscale = dropping(d) ? 1.f / (1.f - d->dropout) : 1.f;
+  a.p = plan.drop ? d->dropout : 0.f;
+  a.gscale = plan.drop ? 1.f / (1.f - d->dropout) : 1.f;
   a.mask = mask;
   int cnt[L1_MAXM];
   for (int m = 0; m < M; ++m) {
@@ -750,11 +750,11 @@ void fill_l1(L1Args& a, const mmf_hybrid_desc* d, const mmf_hybrid_params* W, co
 
 // The L = 1 plan's backward arguments: the L1Args of the forward plus the gradient outputs, and
 // every weight gradient as a dW = G^T X job over the batch (l1_wgrad_kernel)
-void fill_l1_bwd(L1Args& a, L1WgArgs& wa, const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
+void fill_l1_bwd(L1Args& a, L1WgArgs& wa, const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
                  const float* const* x, const float* mask, const Saved& s, const Ws& w, const float* dlogits,
                  const mmf_hybrid_grads* G, float* const* dx) {
   const int B = d->batch, M = d->num_modalities, H = d->hidden, C = d->num_classes;
-  fill_l1(a, d, W, x, mask, s);
+  fill_l1(a, plan, d, W, x, mask, s);
   a.dlogits = dlogits;
   a.dz1 = w.dz1; a.cvec = w.cvec; a.dscore = w.dscore;
   for (int g = 0; g < d->num_pairs; ++g) {
@@ -799,12 +799,23 @@ extern "C" {
 
 size_t mmf_hybrid_saved_bytes(const mmf_hybrid_desc* d) {
   if (check_hybrid(d) != MMF_OK) return 0;
-  return saved_bytes(d);
+  const HybridPlan plan = resolve_plan(d);
+  Bump bp(nullptr);
+  Saved s{};
+  layout_saved(plan, d, bp, s);
+  return bp.off + 256;
 }
 
 size_t mmf_hybrid_workspace_bytes(const mmf_hybrid_desc* d) {
   if (check_hybrid(d) != MMF_OK) return 0;
-  return workspace_bytes(d);
+  const HybridPlan plan = resolve_plan(d);
+  Bump bs(nullptr);
+  Saved s{};
+  layout_saved(plan, d, bs, s);
+  Bump bw(nullptr);
+  Ws w;
+  layout_ws(plan, d, bw, w);
+  return wgrads_top(plan, d, s, w, bw) + 256;
 }
 
 int mmf_hybrid_saved_region(const mmf_hybrid_desc* d, int32_t what, int32_t index, uint64_t* offset,
@@ -812,12 +823,12 @@ int mmf_hybrid_saved_region(const mmf_hybrid_desc* d, int32_t what, int32_t inde
   int rc = check_hybrid(d);
   if (rc) return rc;
   if (!offset || !bytes) return fail(MMF_EINVAL, "saved region: null argument");
-  MathScope math_(d->matmul_precision);
+  const HybridPlan plan = resolve_plan(d);
   // laid out from a stand-in base (never dereferenced; a null base would give null pointers)
   char* const base = reinterpret_cast<char*>(uintptr_t(1) << 40);
   Bump bp(base);
   Saved s{};
-  layout_saved(d, bp, s);
+  layout_saved(plan, d, bp, s);
   const size_t B = d->batch, H = d->hidden;
   const float* p = nullptr;
   size_t n = 0;
@@ -838,21 +849,10 @@ int mmf_hybrid_saved_region(const mmf_hybrid_desc* d, int32_t what, int32_t inde
   return MMF_OK;
 }
 
-namespace {
-
-// dZ_m takes its value-path term E_m as extra K = heads sources of the dZ GEMM
-// (pbarT against the per-sample dU) when a 128-row tile never straddles two
-// samples and the pbarT rows are float4-able; otherwise pool_e materialises E_m.
-bool poole_in_dz(const mmf_hybrid_desc* d, int m) {
-  if (getenv("MMF_NO_POOLE") || dqk_b16_on(d)) return false;
-  return Lm(d, m) % 128 == 0 && d->hidden % 4 == 0 && d->num_heads % 4 == 0;
-}
-
-}  // namespace
 
 // A training step's loss inside the tail's head launch (mmf_hybrid_train_step, the pooled tail plan
 // with the 16-sample tile head): the loss inputs and outputs, the step's sync word (the head
-// launch's tile count) and workspace (dz1, cvec, dscore and the loss rows).  done: the forward's
+// launch's tile count) and workspace slots (dz1, cvec, dscore and the loss rows).  done: the forward's
 // head launch ran the loss, dlogits and the head backward (the step skips the cross-entropy
 // launch, and the backward its head launch).
 struct TailTrain {
@@ -860,38 +860,29 @@ struct TailTrain {
   float ls_eps, loss_scale;
   float *loss, *dlogits;
   uint32_t* cnt;
-  void* workspace;
+  const Ws* w;
   bool done;
 };
 
-static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
-                          const float* mask, const uint64_t* rng_state, void* saved, float* logits,
-                          float* fusion_weights, float* const* attn_maps, void* stream, TailTrain* tt) {
-  int rc = check_hybrid(d);
-  if (rc) return rc;
-  MathScope math_(d->matmul_precision);
-  if (!W || !x || !mask || !saved || !logits) return fail(MMF_EINVAL, "null argument");
+// The forward's launches, on a checked descriptor and a laid-out, checked `saved` (s)
+static int hybrid_forward(const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
+                          const float* const* x, const float* mask, const uint64_t* rng_state, const Saved& s,
+                          float* logits, float* fusion_weights, float* const* attn_maps, void* stream,
+                          TailTrain* tt) {
   hipStream_t st = (hipStream_t)stream;
   const int B = d->batch, M = d->num_modalities, H = d->hidden, C = d->num_classes;
   const int nh = d->num_heads, hd = H / nh;
-  const bool drop = dropping(d);
+  const bool drop = plan.drop;
   const float p = drop ? d->dropout : 0.f;
-  const bool pool = use_pool(d);
-  if (drop && !rng_state) return fail(MMF_EINVAL, "training with dropout needs rng_state");
-
-  Bump bp(saved);
-  Saved s{};
-  layout_saved(d, bp, s);
-  // (against the capacity the caller declared, under the plan switches it sized `saved` with)
-  if ((rc = check_buffers(d, bp.off, ~size_t(0)))) return rc;
+  const bool pool = plan.pool;
   // the rng snapshot {seed, offset} is written by the input-mask kernel (which draws from
   // the live state) and the live offset advanced by the projection GEMM's first launch:
   // no launch of its own
   const RngSnap* rng = rng_state ? s.rng : nullptr;
 
-  if (lean_l1(d, W, x)) {
+  if (lean_l1(plan, d, W, x)) {
     L1Args a;
-    fill_l1(a, d, W, x, mask, s);
+    fill_l1(a, plan, d, W, x, mask, s);
     a.rng_live = rng_state;
     a.rng_advance = const_cast<uint64_t*>(rng_state);
     a.logits = logits;
@@ -908,44 +899,27 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
   std::vector<WidePair> wp;
   for (int g = 0; g < d->num_pairs; ++g) {
     float* maps = d->return_attention && attn_maps ? attn_maps[g] : nullptr;
-    if (single_key(d, g)) {
+    if (plan.sk(g)) {
       skp.push_back(make_sk(d, s, mask, g));
       skp.back().probs = maps;
-    } else if (wide_pair(d, g)) {
+    } else if (plan.wide(g)) {
       wp.push_back(make_wide(d, s, mask, g));
       wp.back().probs = maps;   // written by the wide softmax itself
     } else {
-      pairs.push_back(make_pair(d, s, mask, g));
+      pairs.push_back(make_pair(plan, d, s, mask, g));
       pairs.back().probs = maps;
     }
   }
   const int nmp = (int)pairs.size(), nsk = (int)skp.size(), nwp = (int)wp.size();
-  // The attention dropout keep words depend only on the rng snapshot: drawn on a side stream
-  // (attn_keep_words_kernel) while the projection GEMMs run, so the attention forward reads
-  // them instead of drawing inline.  Pooled plan, training, with long-key pairs (C5: the
-  // draws are a third of the one-pass forward's VALU work; at C2's 128 keys the concurrent
-  // draws slow the fp32 GEMMs more than the lean forward gains, 0.979 -> 0.986 ms); an
-  // existing side stream only while st is being captured.  MMF_NO_SIDE_STREAM=1: inline (A/B);
-  // MMF_SIDE_STREAM=1: also without long pairs.
+  // The attention dropout keep words (HybridPlan::keep_words): when a launch of their own draws them,
+  // it follows the input-mask kernel, which writes the rng snapshot; an existing side stream only
+  // while st is being captured.  have_kw: the attention forward reads them instead of drawing inline.
   SideStream* side = nullptr;
-  // MMF_KW_SERIAL=1 (A/B): the draws on st, ahead of the projection GEMM.  At C2 the lean forward
-  // drops 112-116 -> 90 us but the draw kernel takes 26.5 us: 0.968 -> 0.971-0.975 ms
-  bool kw_serial = false;
-  // Without long-key pairs (and at most 16 pairs) the draws are made by extra workgroups of the
-  // input-mask kernel, interleaved with its HBM-bound rows: at C2 the lean forward drops
-  // 113 -> 91 us and the mask kernel grows 23 -> 41 us, step 0.969 -> 0.960 ms median
-  // (DESIGN §7).  MMF_NO_KW_FUSED=1: off; MMF_KW_FUSED=1: also with long-key pairs.
-  bool kw_fused = false;
-  bool any_long = false;
-  for (const AttnPair& a : pairs) any_long = any_long || a.Lk > 128;
+  bool have_kw = plan.keep_words == KeepWords::MASK_FOLD;
   auto fork_keep_words = [&]() {
-    if (!(drop && use_pool(d) && nmp) || getenv("MMF_NO_SIDE_STREAM")) return;
-    if (kw_fused) return;
-    if (getenv("MMF_KW_SERIAL")) {
-      kw_serial = launch_attn_keep_words(pairs.data(), nmp, B, nh, p, rng, st) == hipSuccess;
-      return;
-    }
-    if (!any_long && !getenv("MMF_SIDE_STREAM")) return;
+    if (plan.keep_words == KeepWords::SERIAL)
+      have_kw = launch_attn_keep_words(pairs.data(), nmp, B, nh, p, rng, st) == hipSuccess;
+    if (plan.keep_words != KeepWords::SIDE_STREAM) return;
     side = side_stream(!prof_capturing(st));
     if (!side) return;
     if (hipEventRecord(side->fork_ev, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork_ev, 0) != hipSuccess ||
@@ -953,11 +927,12 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
         hipEventRecord(side->join_ev, side->s) != hipSuccess) {
       side = nullptr;   // (a failed fork joins nothing; the kernels draw inline)
     }
+    have_kw = side != nullptr;
   };
 
   // (1) per-modality projection: P_m = Drop(ReLU(X'_m W_m^T + b_m)), X'_m = Drop(X_m * mask_m)
   //     (fusion.py:364-374); X' is kept for the weight gradient
-  const bool pb16 = proj_b16_on(d);
+  const bool pb16 = plan.proj_b16;
   bool qk_cvt_done = false;
   if (pb16) {
     // bf16 copies of W_proj and (the Q/K branch below then skips its own launch) W_q / W_k
@@ -967,7 +942,7 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
       cv.src[cv.count] = W->proj[m].w; cv.dst[cv.count] = s.Wpb[m]; cv.n[cv.count++] = (int64_t)H * d->in_dim[m];
     }
     for (int g = 0; g < d->num_pairs; ++g) {
-      if (single_key(d, g) || wide_pair(d, g)) continue;
+      if (plan.sk(g) || plan.wide(g)) continue;
       cv.src[cv.count] = W->q[g].w; cv.dst[cv.count] = s.Wqb[g]; cv.n[cv.count++] = (int64_t)H * H;
       cv.src[cv.count] = W->k[g].w; cv.dst[cv.count] = s.Wkb[g]; cv.n[cv.count++] = (int64_t)H * H;
     }
@@ -997,28 +972,18 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
       add_src(j, opnd(s.Xd[m], D), opnd(W->proj[m].w, D), D);
       jobs.push_back(j);
     }
-    if (drop && use_pool(d) && nmp && !getenv("MMF_NO_SIDE_STREAM") && !getenv("MMF_SIDE_STREAM") &&
-        !getenv("MMF_KW_SERIAL") && !getenv("MMF_NO_KW_FUSED") && (!any_long || getenv("MMF_KW_FUSED"))) {
-      int nkw = 0;
-      bool fits = true;
-      for (const AttnPair& a : pairs) {
-        if (!(a.keep_bits && a.Lk % 32 == 0 && a.Lk > 0 && a.kw_ld >= a.Lk / 32)) continue;
-        // at most 16 pairs, each under launch_mask_dropout's 2^31-word bound: otherwise the
-        // side-stream / inline draws (never a failed forward)
-        const int64_t nw = (int64_t)B * nh * a.Lq * (a.Lk / 32);
-        if (nkw == 16 || nw >= ((int64_t)1 << 31)) { fits = false; break; }
-        ma.kw[nkw++] = {a.keep_bits, (uint32_t)a.Lq, (uint32_t)a.Lk, (uint32_t)a.kw_ld, a.drop_site};
-      }
-      ma.nkw = fits ? nkw : 0;
+    if (plan.keep_words == KeepWords::MASK_FOLD) {
+      for (const AttnPair& a : pairs)
+        if (kw_foldable(a.Lk))
+          ma.kw[ma.nkw++] = {a.keep_bits, (uint32_t)a.Lq, (uint32_t)a.Lk, (uint32_t)a.kw_ld, a.drop_site};
       ma.B = B;
       ma.heads = nh;
-      kw_fused = fits;
-      static bool warned = false;
-      if (!fits && getenv("MMF_KW_FUSED") && !warned) {
-        warned = true;
-        fprintf(stderr, "mmfusion: MMF_KW_FUSED requested but the keep-word fold does not fit "
-                        "(> 16 pairs or > 2^31 words per pair): drawing them on the side stream / inline\n");
-      }
+    }
+    static bool warned = false;
+    if (plan.kw_fold_unfit && !warned) {
+      warned = true;
+      fprintf(stderr, "mmfusion: MMF_KW_FUSED requested but the keep-word fold does not fit "
+                      "(> 16 pairs or > 2^31 words per pair): drawing them on the side stream / inline\n");
     }
     STAGE_TRY("fwd.input_mask", launch_mask_dropout(ma, st));
     fork_keep_words();   // the rng snapshot exists from here on
@@ -1032,9 +997,9 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
     }
   }
   // (2) Q/K (and V for the general plan) projections of every present pair (attention.py:104-106)
-  if (d->num_pairs && qk_cat_on(d)) {
+  if (d->num_pairs && plan.qk_cat) {
     // the stacked bf16 W copies and fp32 biases per modality, then one bf16 GEMM per modality
-    // writing every Q / K column block of it (see qk_cat_on)
+    // writing every Q / K column block of it (see qk_cat)
     std::vector<CvtArgs> cvs(1);
     memset(&cvs[0], 0, sizeof(CvtArgs));
     auto add_cvt = [&](const float* src, __bf16* dst, float* dst32, int64_t n) {
@@ -1046,18 +1011,18 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
       c.src[c.count] = src; c.dst[c.count] = dst; c.dst32[c.count] = dst32; c.n[c.count++] = n;
     };
     for (int g = 0; g < d->num_pairs; ++g) {
-      if (s.qcol[g] < 0) continue;
+      if (plan.qcol[g] < 0) continue;
       const int q = d->pair_q[g], k = d->pair_k[g];
       add_cvt(W->q[g].w, s.Wqb[g], nullptr, (int64_t)H * H);
       add_cvt(W->k[g].w, s.Wkb[g], nullptr, (int64_t)H * H);
-      add_cvt(W->q[g].b, nullptr, s.bc[q] + (size_t)s.qcol[g] * H, H);
-      add_cvt(W->k[g].b, nullptr, s.bc[k] + (size_t)s.kcol[g] * H, H);
+      add_cvt(W->q[g].b, nullptr, s.bc[q] + (size_t)plan.qcol[g] * H, H);
+      add_cvt(W->k[g].b, nullptr, s.bc[k] + (size_t)plan.kcol[g] * H, H);
     }
     std::vector<GemmJob> jobs;
     auto bop = [](const __bf16* p, int ld) { return opnd(reinterpret_cast<const float*>(p), ld); };
     for (int m = 0; m < M; ++m) {
-      if (s.ncat[m] <= 0) continue;
-      const int N = s.ncat[m] * H;
+      if (plan.ncat[m] <= 0) continue;
+      const int N = plan.ncat[m] * H;
       GemmJob j = make_job(B * Lm(d, m), N, reinterpret_cast<float*>(s.QKc[m]), N, EPI_BIAS | EPI_BF16);
       j.g.bias = s.bc[m];
       add_src(j, bop(s.Pb[m], H), bop(s.Wc[m], H), H);
@@ -1065,7 +1030,7 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
     }
     for (const CvtArgs& c : cvs) STAGE_TRY("fwd.qk_cvt", launch_cvt_bf16(c, st));
     STAGE_TRY("fwd.qkv_gemm", launch_gemm_b16(jobs.data(), (int)jobs.size(), st));
-  } else if (d->num_pairs && qk_gemm_b16(d)) {
+  } else if (d->num_pairs && plan.qk_gemm_b16) {
     // bf16 copies of W_q / W_k, then one bf16-operand GEMM launch over every Q / K projection
     CvtArgs cv;
     memset(&cv, 0, sizeof(cv));
@@ -1073,7 +1038,7 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
     auto bop = [](const __bf16* p, int ld) { return opnd(reinterpret_cast<const float*>(p), ld); };
     for (int g = 0; g < d->num_pairs; ++g) {
       const int q = d->pair_q[g], k = d->pair_k[g];
-      if (single_key(d, g) || wide_pair(d, g)) continue;
+      if (plan.sk(g) || plan.wide(g)) continue;
       cv.src[cv.count] = W->q[g].w; cv.dst[cv.count] = s.Wqb[g]; cv.n[cv.count++] = (int64_t)H * H;
       cv.src[cv.count] = W->k[g].w; cv.dst[cv.count] = s.Wkb[g]; cv.n[cv.count++] = (int64_t)H * H;
       GemmJob jq = make_job(B * Lm(d, q), H, s.Q[g], H, EPI_BIAS | EPI_BF16);
@@ -1092,8 +1057,8 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
     for (int g = 0; g < d->num_pairs; ++g) {
       const int q = d->pair_q[g], k = d->pair_k[g];
       const int lq = Lm(d, q), lk = Lm(d, k);
-      if (!single_key(d, g)) {
-        const int qkb = pair_qk_bf16(d, g) ? EPI_BF16 : 0;
+      if (!plan.sk(g)) {
+        const int qkb = plan.pair_qk_bf16[g] ? EPI_BF16 : 0;
         GemmJob jq = make_job(B * lq, H, s.Q[g], H, EPI_BIAS | qkb);
         jq.g.bias = W->q[g].b;
         add_src(jq, opnd(s.P[q], H), opnd(W->q[g].w, H), H);
@@ -1118,7 +1083,7 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
   if (d->num_pairs && pool) {
     // (3p) attention -> LSE, pbar = mean_q P'; U = pbar P_k; Obar = U W_v^T + r b_v; Abar = out_proj
     if (nmp)
-      STAGE_TRY("fwd.attn", launch_attn_pool_fwd(pairs.data(), nmp, B, nh, hd, scale, p, rng, st, side != nullptr || kw_serial || kw_fused));
+      STAGE_TRY("fwd.attn", launch_attn_pool_fwd(pairs.data(), nmp, B, nh, hd, scale, p, rng, st, have_kw));
     if (nsk) STAGE_TRY("fwd.attn_single_key", launch_sk_fwd(skp.data(), nsk, B, nh, hd, p, rng, st));
     if (nwp) STAGE_TRY("fwd.attn_wide", launch_wide_fwd(wp.data(), nwp, B, nh, hd, scale, p, rng, true, st));
     std::vector<PoolPair> pp(d->num_pairs);
@@ -1130,17 +1095,15 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
       pp[g].u = s.U[g];
       pp[g].r = s.r[g];
     }
-    if (use_tail(d)) {
+    if (plan.tail) {
       // (4p) fused per-sample tail: Obar, Abar, aggregation, weighting, classifier
       TailArgs ta;
-      fill_tail(ta, d, W, mask, s);
+      fill_tail(ta, plan, d, W, mask, s);
       ta.weights_out = fusion_weights;
       ta.logits = logits;
       if (tt && seq_head_ok(ta)) {
         // (a training step: the loss, dlogits and the head backward in the head launch)
-        Bump bw(tt->workspace);
-        Ws w;
-        layout_ws(d, bw, w);
+        const Ws& w = *tt->w;
         ta.labels = tt->labels; ta.ls_eps = tt->ls_eps; ta.loss_scale = tt->loss_scale;
         ta.loss_rows = w.dfused;   // (B x H floats the tail plan leaves unused)
         ta.loss_mean = tt->loss; ta.loss_cnt = tt->cnt; ta.dlogits_out = tt->dlogits;
@@ -1189,9 +1152,9 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
   }
   // (4) aggregation + pooling + gating + adaptive weights + weighted sum (fusion.py:406-418)
   // (5) classifier: Linear -> ReLU -> Dropout -> Linear (fusion.py:323-328)
-  if (!(d->num_pairs && use_tail(d))) {
+  if (!plan.tail) {
     HeadArgs ha;
-    fill_head(ha, d, W, mask, s);
+    fill_head(ha, plan, d, W, mask, s);
     ha.weights_out = fusion_weights;
     STAGE_TRY("fwd.head", launch_head_fwd(ha, st));
     GemmJob j = make_job(B, H, s.h1, H, EPI_BIAS | EPI_RELU | (drop ? EPI_DROP : 0));
@@ -1232,56 +1195,59 @@ static int hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
 int mmf_hybrid_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
                        const float* mask, const uint64_t* rng_state, void* saved, float* logits,
                        float* fusion_weights, float* const* attn_maps, void* stream) {
-  return hybrid_forward(d, W, x, mask, rng_state, saved, logits, fusion_weights, attn_maps, stream, nullptr);
+  int rc = check_hybrid(d);
+  if (rc) return rc;
+  MathScope math_(d->matmul_precision);
+  if (!W || !x || !mask || !saved || !logits) return fail(MMF_EINVAL, "null argument");
+  const HybridPlan plan = resolve_plan(d);
+  if (plan.drop && !rng_state) return fail(MMF_EINVAL, "training with dropout needs rng_state");
+  Bump bp(saved);
+  Saved s{};
+  layout_saved(plan, d, bp, s);
+  // (against the capacity the caller declared, under the plan switches it sized `saved` with)
+  if ((rc = check_buffers(plan, d, bp.off, ~size_t(0)))) return rc;
+  return hybrid_forward(plan, d, W, x, mask, rng_state, s, logits, fusion_weights, attn_maps, stream, nullptr);
 }
 
 // head_done: the training step's head launch ran the head backward (TailTrain)
 // part: 0 the whole backward; 1 everything up to the attention backward and every weight gradient
 // but the modality projections'; 2 dZ, dX and the projections' weight gradients (the L = 1 plan
 // runs all of it in part 1)
-static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
-                           const float* mask, const void* saved, const float* dlogits, void* workspace,
-                           const mmf_hybrid_grads* G, float* const* dx, void* stream, bool head_done,
-                           int part = 0) {
-  int rc = check_hybrid(d);
-  if (rc) return rc;
-  MathScope math_(d->matmul_precision);
-  if (!W || !x || !mask || !saved || !dlogits || !workspace || !G)
-    return fail(MMF_EINVAL, "null argument");
+// On a checked descriptor and laid-out buffers: s with its extent need_saved; w with bw, the
+// workspace past the Ws slots (the weight-gradient slabs are planned from there, then both
+// buffers checked against their capacities)
+static int hybrid_backward(const HybridPlan& plan, const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
+                           const float* const* x, const float* mask, const Saved& s, size_t need_saved,
+                           const float* dlogits, const Ws& w, Bump bw, const mmf_hybrid_grads* G,
+                           float* const* dx, void* stream, bool head_done, int part = 0) {
+  int rc;
   hipStream_t st = (hipStream_t)stream;
   const int B = d->batch, M = d->num_modalities, H = d->hidden, C = d->num_classes;
   const int nh = d->num_heads, hd = H / nh;
-  const bool drop = dropping(d);
+  const bool drop = plan.drop;
   const float p = drop ? d->dropout : 0.f;
   const float gscale = drop ? 1.f / (1.f - p) : 1.f;
-  const bool pool = use_pool(d);
-
-  Bump bs(const_cast<void*>(saved));
-  Saved s{};
-  layout_saved(d, bs, s);
+  const bool pool = plan.pool;
   const RngSnap* rng = s.rng;
-  Bump bw(workspace);
-  Ws w;
-  layout_ws(d, bw, w);
-  if (lean_l1(d, W, x)) {
-    if ((rc = check_buffers(d, bs.off, bw.off))) return rc;
+  if (lean_l1(plan, d, W, x)) {
+    if ((rc = check_buffers(plan, d, need_saved, bw.off))) return rc;
     if (part == 2) return MMF_OK;
     L1Args a;
     L1WgArgs wa;
-    fill_l1_bwd(a, wa, d, W, x, mask, s, w, dlogits, G, dx);
+    fill_l1_bwd(a, wa, plan, d, W, x, mask, s, w, dlogits, G, dx);
     STAGE_TRY("bwd.l1", launch_l1_backward(a, wa, st));
     return MMF_OK;
   }
   WgradPlan wp;
-  plan_wgrads(d, x, mask, dlogits, s, w, G, bw, wp, part);
-  if ((rc = check_buffers(d, bs.off, bw.off))) return rc;
+  plan_wgrads(plan, d, x, mask, dlogits, s, w, G, bw, wp, part);
+  if ((rc = check_buffers(plan, d, need_saved, bw.off))) return rc;
 
-  const bool tail = d->num_pairs && use_tail(d);
+  const bool tail = plan.tail;
   if (part != 2) {
   if (tail) {
     // (1-3p) fused per-sample tail backward: classifier, head, dObar, dU
     TailArgs ta;
-    fill_tail(ta, d, W, mask, s);
+    fill_tail(ta, plan, d, W, mask, s);
     ta.dlogits = dlogits; ta.dz1 = w.dz1; ta.cvec = w.cvec; ta.dscore = w.dscore;
     ta.head_done = head_done;
     for (int g = 0; g < d->num_pairs; ++g) {
@@ -1304,7 +1270,7 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
     // (2) head backward: dscore and c_m = dpooled_m * mask_m / n_m
     {
       HeadArgs ha;
-      fill_head(ha, d, W, mask, s);
+      fill_head(ha, plan, d, W, mask, s);
       ha.dfused = w.dfused; ha.cvec = w.cvec; ha.dscore = w.dscore;
       STAGE_TRY("bwd.head", launch_head_bwd(ha, st));
     }
@@ -1314,20 +1280,20 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
   std::vector<SkPair> skp;
   std::vector<WidePair> wpairs;
   for (int g = 0; g < d->num_pairs; ++g) {
-    if (single_key(d, g)) {
+    if (plan.sk(g)) {
       skp.push_back(make_sk(d, s, mask, g));
       skp.back().dout = w.dO[g];
       skp.back().dv = w.dV[g];
       continue;
     }
-    if (wide_pair(d, g)) {
+    if (plan.wide(g)) {
       wpairs.push_back(make_wide(d, s, mask, g));
       WidePair& a = wpairs.back();
       a.dpbar = w.dpbar[g]; a.dout = w.dO[g]; a.dPd = w.dPd[g]; a.dS = w.dS[g];
       a.dq = w.dQ[g]; a.dk = w.dK[g]; a.dv = w.dV[g];
       continue;
     }
-    pairs.push_back(make_pair(d, s, mask, g));
+    pairs.push_back(make_pair(plan, d, s, mask, g));
     AttnPair& a = pairs.back();
     a.dsum = w.dsum[g]; a.dq = w.dQ[g]; a.dk = w.dK[g];
     a.dout = w.dO[g]; a.dv = w.dV[g]; a.dpbar = w.dpbar[g];
@@ -1372,8 +1338,9 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
       hipError_t fe;
       {
         Stage stage_("bwd.attn", st);
-        fe = getenv("MMF_NO_FUSED_BWD") ? hipErrorNotSupported
-                                        : launch_attn_pool_bwd(2, pairs.data(), nmp, B, nh, hd, scale, p, rng, st);
+        // (MMF_NO_FUSED_BWD=1: the two-pass kernels, A/B)
+        fe = !plan.fused_bwd ? hipErrorNotSupported
+                             : launch_attn_pool_bwd(2, pairs.data(), nmp, B, nh, hd, scale, p, rng, st);
       }
       if (fe == hipErrorNotSupported) {
         (void)hipGetLastError();
@@ -1389,7 +1356,7 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
     if (nwp) STAGE_TRY("bwd.attn_wide", launch_wide_bwd(wpairs.data(), nwp, B, nh, hd, scale, p, rng, true, st));
     std::vector<PoolEMod> em;
     for (int m = 0; m < M; ++m) {
-      if (poole_in_dz(d, m)) continue;   // E_m is formed in the dZ GEMM's epilogue instead
+      if (plan.poole_in_dz[m]) continue;   // E_m is formed in the dZ GEMM's epilogue instead
       em.emplace_back();
       PoolEMod& e = em.back();
       memset(&e, 0, sizeof(PoolEMod));
@@ -1444,31 +1411,27 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
   // of its own
   std::vector<GemmJob> dxjobs(M);
   std::vector<bool> has_dx(M, false);
-  const bool pb16 = proj_b16_on(d);
+  const bool pb16 = plan.proj_b16;
   for (int m = 0; m < M; ++m) {
     if (!dx || !dx[m]) continue;
     const int L = Lm(d, m), D = d->in_dim[m];
     GemmJob j = make_job(B * L, D, dx[m], D, EPI_ROWSCALE | (drop ? EPI_DROP : 0));
     j.g.rowscale = mask; j.g.rs_div = L; j.g.rs_stride = M; j.g.rs_off = m;
     j.g.drop_site = SITE_IN + m;
-    // (proj_b16_on: the bf16 dZ against the forward's W_proj copy, launch_gemm_b16's RK x KR form)
+    // (proj_b16: the bf16 dZ against the forward's W_proj copy, launch_gemm_b16's RK x KR form)
     add_src(j, opnd(w.dZ[m], H), opnd(pb16 ? reinterpret_cast<const float*>(s.Wpb[m]) : W->proj[m].w, D), H);
     dxjobs[m] = j;
     has_dx[m] = true;
   }
-  // Opt-in (MMF_DX_CHAIN=1): measured at C2 it saves nothing -- the chained kernel took 192.2 us
-  // for what the two launches take in 191.1 (profiles/r06/dx_chain/): every workgroup still runs
-  // dZ's epilogue, then dX's prologue, main loop and epilogue in lockstep with all the others, so
-  // the chain removes only the launch boundary and dZ's HBM re-read, neither of which bounds it
-  const bool chain_dx = !dqk_b16_on(d) && !pb16 && getenv("MMF_DX_CHAIN");
+  const bool chain_dx = plan.dx_chain;   // (opt-in: it measured no gain, see resolve_plan)
   // (4) dZ_m = gate(P_m) * [direct + sum_q dQ W_q + sum_k dK W_k (+ dV W_v)]
   {
     std::vector<GemmJob> jobs;
     for (int m = 0; m < M; ++m) {
       const int L = Lm(d, m);
-      const bool pe = pool && poole_in_dz(d, m);
+      const bool pe = pool && plan.poole_in_dz[m];
       GemmJob j = make_job(B * L, H, w.dZ[m], H,
-                           EPI_GATE | (pool && !pe ? EPI_ADDMAT : EPI_ROWADD) | (proj_b16_on(d) ? EPI_BF16 : 0));
+                           EPI_GATE | (pool && !pe ? EPI_ADDMAT : EPI_ROWADD) | (plan.proj_b16 ? EPI_BF16 : 0));
       if (pool && !pe) {
         j.g.addm = w.E[m];
         j.g.ld_addm = H;
@@ -1480,21 +1443,21 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
       }
       j.g.gate = s.P[m];
       j.g.ld_gate = H;
-      // (proj_b16_on: the sign of P_m from its bf16 copy -- half the gate bytes; MMF_NO_GATE_B16=1 A/B)
-      if (proj_b16_on(d) && s.Pb[m] && !getenv("MMF_NO_GATE_B16")) {
+      // (gate_b16: the sign of P_m from its bf16 copy)
+      if (plan.gate_b16 && s.Pb[m]) {
         j.g.gate = reinterpret_cast<const float*>(s.Pb[m]);
         j.g.epi |= EPI_GATE_B16;
       }
       j.g.gate_scale = gscale;
-      const bool b16 = dqk_b16_on(d);
-      if (b16 && qk_cat_on(d)) {
+      const bool b16 = plan.dqk_b16;
+      if (b16 && plan.qk_cat) {
         // one source: the modality's dQ / dK block matrix against its stacked W copies (K = ncat H,
         // the slots in the order the separate sources had)
-        if (s.ncat[m] > 0)
-          add_src(j, opnd(w.dQc[m], s.ncat[m] * H), opnd(reinterpret_cast<const float*>(s.Wc[m]), H), s.ncat[m] * H);
+        if (plan.ncat[m] > 0)
+          add_src(j, opnd(w.dQc[m], plan.ncat[m] * H), opnd(reinterpret_cast<const float*>(s.Wc[m]), H), plan.ncat[m] * H);
       } else {
         for (int g = 0; g < d->num_pairs; ++g) {
-          const bool sk = single_key(d, g);
+          const bool sk = plan.sk(g);
           // (bf16: dQ / dK and the forward's W_q / W_k copies, launch_gemm_b16's RK x KR form)
           const float* wq = b16 ? reinterpret_cast<const float*>(s.Wqb[g]) : W->q[g].w;
           const float* wk = b16 ? reinterpret_cast<const float*>(s.Wkb[g]) : W->k[g].w;
@@ -1521,7 +1484,7 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
       jobs.push_back(j);
     }
     // (the dX_m of a chained launch take its dropout p: the dZ epilogue has no dropout site)
-    if (dqk_b16_on(d)) STAGE_TRY("bwd.dZ_gemm", launch_gemm_b16(jobs.data(), (int)jobs.size(), st, MODE_RK, MODE_KR));
+    if (plan.dqk_b16) STAGE_TRY("bwd.dZ_gemm", launch_gemm_b16(jobs.data(), (int)jobs.size(), st, MODE_RK, MODE_KR));
     else STAGE_TRY("bwd.dZ_gemm", launch_gemm(jobs.data(), (int)jobs.size(), MODE_RK, MODE_KR, chain_dx ? p : 0.f, rng, st));
   }
   // (5) dX_m, unless chained above
@@ -1551,14 +1514,26 @@ static int hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W,
 int mmf_hybrid_backward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
                         const float* mask, const void* saved, const float* dlogits, void* workspace,
                         const mmf_hybrid_grads* G, float* const* dx, void* stream) {
-  return hybrid_backward(d, W, x, mask, saved, dlogits, workspace, G, dx, stream, false);
+  int rc = check_hybrid(d);
+  if (rc) return rc;
+  MathScope math_(d->matmul_precision);
+  if (!W || !x || !mask || !saved || !dlogits || !workspace || !G)
+    return fail(MMF_EINVAL, "null argument");
+  const HybridPlan plan = resolve_plan(d);
+  Bump bs(const_cast<void*>(saved));
+  Saved s{};
+  layout_saved(plan, d, bs, s);
+  Bump bw(workspace);
+  Ws w;
+  layout_ws(plan, d, bw, w);
+  return hybrid_backward(plan, d, W, x, mask, s, bs.off, dlogits, w, bw, G, dx, stream, false);
 }
 
-uint32_t mmf_hybrid_plan_flags(void) { return plan_flags_now(); }
+uint32_t mmf_hybrid_plan_flags(void) { return plan_fingerprint(); }
 
 int mmf_hybrid_lean_l1(const mmf_hybrid_desc* d) {
   if (check_hybrid(d) != MMF_OK) return 0;
-  return lean_l1_desc(d) ? 1 : 0;
+  return resolve_plan(d).lean_l1 ? 1 : 0;
 }
 
 size_t mmf_hybrid_train_sync_bytes(const mmf_hybrid_desc* d) {
@@ -1606,22 +1581,25 @@ int mmf_hybrid_train_step_part(int part, const mmf_hybrid_desc* d, const mmf_hyb
     return fail(MMF_EINVAL, "null argument");
   if (clip_partial && !step_dev) return fail(MMF_EINVAL, "train step: clip partials need the step counter");
   if (clip_partial && part != 0) return fail(MMF_EINVAL, "train step: clip partials need the whole step (part 0)");
+  MathScope math_(d->matmul_precision);
+  // the step's plan and both buffers' layouts, once: the launch-lean step, the forward and the
+  // backward below all take these
+  const HybridPlan plan = resolve_plan(d);
+  Bump bs(saved);
+  Saved s{};
+  layout_saved(plan, d, bs, s);
+  Bump bw(workspace);
+  Ws w;
+  layout_ws(plan, d, bw, w);
   // (the one-launch kernel needs its tiles x pairs workgroups resident at once, one per CU)
-  if (sync && lean_l1(d, W, x) &&
-      (int64_t)((d->batch + 15) / 16) * d->num_pairs <= l1_train_capacity(l1_desc_full(d))) {
+  if (sync && lean_l1(plan, d, W, x) &&
+      (int64_t)((d->batch + 15) / 16) * d->num_pairs <= l1_train_capacity(plan.l1_full)) {
     if (part == 2) return MMF_OK;   // (every gradient came out of part 1's launches)
-    MathScope math_(d->matmul_precision);
     hipStream_t st = (hipStream_t)stream;
-    Bump bs(saved);
-    Saved s{};
-    layout_saved(d, bs, s);
-    Bump bw(workspace);
-    Ws w;
-    layout_ws(d, bw, w);
-    if ((rc = check_buffers(d, bs.off, bw.off))) return rc;
+    if ((rc = check_buffers(plan, d, bs.off, bw.off))) return rc;
     L1Args a;
     L1WgArgs wa;
-    fill_l1_bwd(a, wa, d, W, x, mask, s, w, dlogits, G, dx);
+    fill_l1_bwd(a, wa, plan, d, W, x, mask, s, w, dlogits, G, dx);
     a.rng_live = rng_state;
     a.rng_advance = rng_state;
     a.logits = logits;
@@ -1639,27 +1617,25 @@ int mmf_hybrid_train_step_part(int part, const mmf_hybrid_desc* d, const mmf_hyb
     STAGE_TRY("train.l1", launch_l1_train(a, wa, st));
     return MMF_OK;
   }
-  {
-    // the whole step's buffers before its first launch (the forward's launches would otherwise
-    // run before the backward's workspace check)
-    MathScope math_(d->matmul_precision);
-    if ((rc = check_buffers(d, saved_bytes(d) - 256, workspace_bytes(d) - 256))) return rc;
-  }
+  // the whole step's buffers before its first launch (the forward's launches would otherwise
+  // run before the backward's workspace check): the workspace of any part
+  if ((rc = check_buffers(plan, d, bs.off, wgrads_top(plan, d, s, w, bw)))) return rc;
   if (part == 2) {
     // the head-done flag of part 1's forward: the same decision, from the same descriptor and
     // pointers (only the backward's tail launch depends on it, and part 2 runs none)
-    return hybrid_backward(d, W, x, mask, saved, dlogits, workspace, G, dx, stream, false, 2);
+    return hybrid_backward(plan, d, W, x, mask, s, bs.off, dlogits, w, bw, G, dx, stream, false, 2);
   }
+  if (plan.drop && !rng_state) return fail(MMF_EINVAL, "training with dropout needs rng_state");
   // (with the sync words: the pooled tail plan runs the loss and the head backward in its head launch)
-  TailTrain tt{labels, label_smoothing, loss_scale, loss_out, dlogits, static_cast<uint32_t*>(sync), workspace, false};
-  rc = hybrid_forward(d, W, x, mask, rng_state, saved, logits, fusion_weights, nullptr, stream, sync ? &tt : nullptr);
+  TailTrain tt{labels, label_smoothing, loss_scale, loss_out, dlogits, static_cast<uint32_t*>(sync), &w, false};
+  rc = hybrid_forward(plan, d, W, x, mask, rng_state, s, logits, fusion_weights, nullptr, stream, sync ? &tt : nullptr);
   if (rc) return rc;
   if (!tt.done) {
     rc = mmf_cross_entropy_ls(d->batch, d->num_classes, logits, labels, label_smoothing, loss_scale, loss_out,
                               dlogits, stream);
     if (rc) return rc;
   }
-  rc = hybrid_backward(d, W, x, mask, saved, dlogits, workspace, G, dx, stream, tt.done, part);
+  rc = hybrid_backward(plan, d, W, x, mask, s, bs.off, dlogits, w, bw, G, dx, stream, tt.done, part);
   if (rc || !clip_partial) return rc;
   if (!grad_flat || grad_n < 0 || (reinterpret_cast<uintptr_t>(grad_flat) & 15))
     return fail(MMF_EINVAL, "train step: clip partials need the 16-byte aligned flat gradient");

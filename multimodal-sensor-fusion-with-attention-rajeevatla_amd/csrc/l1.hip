@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "mmf_device.h"
+#include "mmf_env.h"
 
 namespace mmf {
 namespace {
@@ -1554,7 +1555,7 @@ __global__ __launch_bounds__(NT) void l1_wgrad_kernel(const L1WgArgs w) {
 // s_sleep between polls); MMF_L1_POLL_BOUND overrides it (the timeout test sets 0: every waiter
 // times out at once)
 unsigned l1_poll_bound() {
-  const char* e = getenv("MMF_L1_POLL_BOUND");
+  const char* e = switch_value<SW_L1_POLL_BOUND>();
   return e ? (unsigned)strtoul(e, nullptr, 0) : (1u << 22);
 }
 
@@ -1714,7 +1715,7 @@ hipError_t launch_l1_train(const L1Args& a, const L1WgArgs& w_in, hipStream_t st
 }
 
 bool seq_head_ok(const TailArgs& t) {
-  const bool off = getenv("MMF_TAIL_HEAD_GEMV") != nullptr;   // (the per-sample kernels, for A/B)
+  const bool off = switch_set<SW_TAIL_HEAD_GEMV>();   // (the per-sample kernels, for A/B)
   if (off || t.H > L1_MAXH || t.H % 4 != 0 || t.M < 1 || t.M > L1_MAXM || t.npairs > L1_MAXP || t.C > L1_MAXC ||
       t.C < 1)
     return false;

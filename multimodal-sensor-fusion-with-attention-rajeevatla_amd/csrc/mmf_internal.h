@@ -209,7 +209,7 @@ int device_cu_count();   // CUs of the current device (cached)
 // (the masked, input-dropped modality features of src/fusion.py:364-373,
 // materialised once for the projection GEMM and its weight gradient).
 // outb: X' stored as bf16 (round to nearest even; `out` holds a __bf16 address): the operand the
-// bf16-operand projection GEMM and its weight gradient read (hybrid.hip proj_b16_on)
+// bf16-operand projection GEMM and its weight gradient read (hybrid.hip HybridPlan::proj_b16)
 struct MaskDropJob {
   const float* x; float* out;
   int64_t rows; int32_t D, L;
@@ -293,7 +293,7 @@ struct AttnPair {
   int32_t qk_bf16;
   // dQ and dK written as bf16 (the fused one-pass backward; ldq / ldk in elements): "medium" with
   // every Q/K pair bf16, whose dZ and weight-gradient GEMMs then read bf16 operands (hybrid.hip
-  // dqk_b16_on)
+  // HybridPlan::dqk_b16)
   int32_t dqk_bf16;
 };
 

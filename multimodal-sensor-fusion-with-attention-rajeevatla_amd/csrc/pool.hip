@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mmf_device.h"
+#include "mmf_env.h"
 
 namespace mmf {
 
@@ -478,9 +479,9 @@ __global__ __launch_bounds__(NT, 2) void pool_u_mfma_kernel(const PoolGrpArgs a)
 bool launch_pool_grouped(bool fwd, const PoolPair* pairs, int npairs, int B, int heads, int hd, int H,
                          hipStream_t st, hipError_t& err) {
   err = hipSuccess;
-  if (getenv("MMF_POOL_PER_PAIR") || H % 4 != 0 || H > 256 || npairs < 2) return false;
+  if (switch_set<SW_POOL_PER_PAIR>() || H % 4 != 0 || H > 256 || npairs < 2) return false;
   // the fp32-MFMA forms (MMF_POOL_VALU=1: the VALU forms, A/B)
-  static const bool valu = getenv("MMF_POOL_VALU") != nullptr;
+  const bool valu = switch_set<SW_POOL_VALU>();
   std::vector<std::vector<int>> groups;
   std::vector<const float*> keyp;
   for (int g = 0; g < npairs; ++g) {
@@ -702,10 +703,10 @@ __global__ __launch_bounds__(NT) void pool_e_mfma_kernel(const PoolEArgs a) {
 
 hipError_t launch_pool_e(const PoolEMod* mods, int nmods, int B, int heads, int H, hipStream_t st) {
   if (nmods > 8 || H % 4 != 0) return hipErrorInvalidValue;
-  bool blk = H <= 256 && !getenv("MMF_POOLE_FLAT");
+  bool blk = H <= 256 && !switch_set<SW_POOLE_FLAT>();
   for (int i = 0; i < nmods && blk; ++i) blk = mods[i].nsrc * heads <= POOLE_NSH;
   // the MFMA form: H % 128 (column blocks), 16-B aligned rows (MMF_POOL_VALU=1: the VALU form)
-  static const bool valu = getenv("MMF_POOL_VALU") != nullptr;
+  const bool valu = switch_set<SW_POOL_VALU>();
   bool mf = blk && !valu && H % 128 == 0;
   for (int i = 0; i < nmods && mf; ++i)
     mf = ((uintptr_t)mods[i].out & 15) == 0 && ((uintptr_t)mods[i].c & 15) == 0 && mods[i].ldc % 4 == 0;

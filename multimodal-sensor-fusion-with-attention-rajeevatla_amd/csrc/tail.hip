@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "mmf_device.h"
+#include "mmf_env.h"
 
 namespace mmf {
 
@@ -1027,7 +1028,7 @@ __global__ __launch_bounds__(NT) void tail_head_bwd_kernel(const TailArgs a) {
 int tail_samples() {
   static int s = 0;
   if (s == 0) {
-    const char* e = getenv("MMF_TAIL_S");
+    const char* e = switch_value<SW_TAIL_S>();
     s = e ? atoi(e) : 1;
     if (s != 1 && s != 2 && s != 4) s = 1;
   }
@@ -1041,7 +1042,7 @@ bool tail_supported(int M, int H, int C, int heads, int hd, int npairs) {
 
 // Prefetching head kernels (MMF_TAIL_GEMV=1 also selects the plain ones, for A/B)
 static bool head_pre(const TailArgs& a) {
-  static const bool gemv = getenv("MMF_TAIL_GEMV") != nullptr;
+  const bool gemv = switch_set<SW_TAIL_GEMV>();
   bool allcol = true;
   for (int m = 0; m < a.M; ++m) allcol = allcol && a.Pcol[m] != nullptr;
   return !gemv && allcol && a.H == PH && a.M <= 4 && a.C <= 8;
@@ -1050,7 +1051,7 @@ static bool head_pre(const TailArgs& a) {
 // Groups the pairs by key modality into `m` and reports whether the MFMA pair
 // tail applies (MMF_TAIL_GEMV=1 forces the per-sample GEMV kernels, for A/B).
 static bool tail_mfma_groups(TailArgs& m) {
-  static const bool gemv = getenv("MMF_TAIL_GEMV") != nullptr;
+  const bool gemv = switch_set<SW_TAIL_GEMV>();
   if (gemv || m.H != WH || (m.hd != 32 && m.hd != 64)) return false;
   int mod_of[8];
   m.nkg = 0;
@@ -1103,7 +1104,7 @@ hipError_t launch_tail_fwd(const TailArgs& a, hipStream_t st) {
     // at H = 256 the forward's weight reads (2 x 256 KB per pair) outweigh the lost
     // parallelism: 2 samples per workgroup (C4: 42.2 -> 35.7 us; the backward stays at 1:
     // 45.3 -> 56.6 us at 2)
-    const int S = getenv("MMF_TAIL_S") ? tail_samples() : (a.H >= 256 ? 2 : 1);
+    const int S = switch_set<SW_TAIL_S>() ? tail_samples() : (a.H >= 256 ? 2 : 1);
     if (S == 4) mmf_launch(tail_pair_fwd_kernel<4>, dim3((a.B + 3) / 4, a.npairs), dim3(NT), 0, st, a);
     else if (S == 2) mmf_launch(tail_pair_fwd_kernel<2>, dim3((a.B + 1) / 2, a.npairs), dim3(NT), 0, st, a);
     else mmf_launch(tail_pair_fwd_kernel<1>, dim3(a.B, a.npairs), dim3(NT), 0, st, a);
