@@ -29,20 +29,24 @@ def _sig(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def lstm_forward(x: np.ndarray, w_ih: np.ndarray, w_hh: np.ndarray, b_ih: np.ndarray, b_hh: np.ndarray):
-    """One layer, zero initial state.  x (B, T, D) -> h, c (B, T, H), gates (B, T, 4H) activated."""
-    x = x.astype(np.float64)
+def lstm_forward(x: np.ndarray, w_ih: np.ndarray, w_hh: np.ndarray, b_ih: np.ndarray, b_hh: np.ndarray,
+                 dtype=np.float64, hook=None):
+    """One layer, zero initial state.  x (B, T, D) -> h, c (B, T, H), gates (B, T, 4H) activated.
+    Every array and operation of the run is of `dtype` (np.float32: genuine fp32 arithmetic, the
+    yardstick of tests/_rec.compare).  hook("h_prev", t, h_{t-1}, h) may replace the operand of step
+    t's recurrent product (tests/test_recurrence_bite.py plants defects through it)."""
+    x = x.astype(dtype)
     B, T, _ = x.shape
     H = w_hh.shape[1]
-    xproj = x @ w_ih.astype(np.float64).T + (b_ih.astype(np.float64) + b_hh.astype(np.float64))
-    whh = w_hh.astype(np.float64)
-    h = np.zeros((B, T, H))
-    c = np.zeros((B, T, H))
-    gates = np.zeros((B, T, 4 * H))
-    hp = np.zeros((B, H))
-    cp = np.zeros((B, H))
+    xproj = x @ w_ih.astype(dtype).T + (b_ih.astype(dtype) + b_hh.astype(dtype))
+    whh = w_hh.astype(dtype)
+    h = np.zeros((B, T, H), dtype)
+    c = np.zeros((B, T, H), dtype)
+    gates = np.zeros((B, T, 4 * H), dtype)
+    hp = np.zeros((B, H), dtype)
+    cp = np.zeros((B, H), dtype)
     for t in range(T):
-        pre = xproj[:, t] + hp @ whh.T
+        pre = xproj[:, t] + (hp if hook is None else hook("h_prev", t, hp, h)) @ whh.T
         i, f = _sig(pre[:, :H]), _sig(pre[:, H:2 * H])
         g, o = np.tanh(pre[:, 2 * H:3 * H]), _sig(pre[:, 3 * H:])
         cp = f * cp + i * g
@@ -52,14 +56,17 @@ def lstm_forward(x: np.ndarray, w_ih: np.ndarray, w_hh: np.ndarray, b_ih: np.nda
     return h, c, gates
 
 
-def lstm_backward(w_hh: np.ndarray, c: np.ndarray, gates: np.ndarray, dh: np.ndarray) -> np.ndarray:
+def lstm_backward(w_hh: np.ndarray, c: np.ndarray, gates: np.ndarray, dh: np.ndarray, dtype=np.float64,
+                  hook=None) -> np.ndarray:
     """BPTT: dh (B, T, H) upstream gradient of every h_t -> dgates (B, T, 4H), the gradient of
-    the pre-activation gates (= d xproj; dW_hh = sum_t dgates_t^T h_{t-1})."""
+    the pre-activation gates (= d xproj; dW_hh = sum_t dgates_t^T h_{t-1}), in `dtype` throughout.
+    hook("carry", t, (dh_rec, dc), dgates_t, whh) may replace what step t hands to step t - 1."""
+    c, gates, dh = c.astype(dtype), gates.astype(dtype), dh.astype(dtype)
     B, T, H = c.shape
-    whh = w_hh.astype(np.float64)
-    dgates = np.zeros((B, T, 4 * H))
-    dh_rec = np.zeros((B, H))
-    dc = np.zeros((B, H))
+    whh = w_hh.astype(dtype)
+    dgates = np.zeros((B, T, 4 * H), dtype)
+    dh_rec = np.zeros((B, H), dtype)
+    dc = np.zeros((B, H), dtype)
     for t in range(T - 1, -1, -1):
         i, f = gates[:, t, :H], gates[:, t, H:2 * H]
         g, o = gates[:, t, 2 * H:3 * H], gates[:, t, 3 * H:]
@@ -73,6 +80,8 @@ def lstm_backward(w_hh: np.ndarray, c: np.ndarray, gates: np.ndarray, dh: np.nda
         dgates[:, t] = dg
         dc = dc * f
         dh_rec = dg @ whh
+        if hook is not None:
+            dh_rec, dc = hook("carry", t, (dh_rec, dc), dg, whh)
     return dgates
 
 

@@ -1,4 +1,4 @@
-"""NumPy float64 oracle of the GRU recurrence (test helper, not collected).
+"""NumPy oracle of the GRU recurrence, float64 unless asked for fp32 (test helper, not collected).
 
 PyTorch nn.GRU semantics, gate order r, z, n, zero initial state.  The caller supplies the
 time-parallel part xproj = x W_ih^T + b_ih + [b_hr, b_hz, 0] (B, T, 3H):
@@ -23,16 +23,18 @@ def _sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def gru_forward(xproj, w_hh, b_hn):
-    """-> h (B, T, H), gates (B, T, 4H), float64."""
-    xproj, w_hh, b_hn = (np.asarray(v, np.float64) for v in (xproj, w_hh, b_hn))
+def gru_forward(xproj, w_hh, b_hn, dtype=np.float64, hook=None):
+    """-> h (B, T, H), gates (B, T, 4H); every array and operation of the run in `dtype` (np.float32:
+    genuine fp32 arithmetic).  hook("h_prev", t, h_{t-1}, h) may replace the operand of step t's
+    recurrent product (tests/test_recurrence_bite.py plants defects through it)."""
+    xproj, w_hh, b_hn = (np.asarray(v, dtype) for v in (xproj, w_hh, b_hn))
     B, T, H3 = xproj.shape
     H = H3 // 3
-    h = np.zeros((B, T, H))
-    gates = np.zeros((B, T, 4 * H))
-    prev = np.zeros((B, H))
+    h = np.zeros((B, T, H), dtype)
+    gates = np.zeros((B, T, 4 * H), dtype)
+    prev = np.zeros((B, H), dtype)
     for t in range(T):
-        a = prev @ w_hh.T
+        a = (prev if hook is None else hook("h_prev", t, prev, h)) @ w_hh.T
         r = _sigmoid(xproj[:, t, :H] + a[:, :H])
         z = _sigmoid(xproj[:, t, H:2 * H] + a[:, H:2 * H])
         q = a[:, 2 * H:] + b_hn
@@ -43,21 +45,24 @@ def gru_forward(xproj, w_hh, b_hn):
     return h, gates
 
 
-def gru_backward(w_hh, h, gates, dh):
-    """-> dgates (B, T, 4H) = [dr_pre, dz_pre, dn_pre, dn_pre * r], float64."""
-    w_hh, h, gates, dh = (np.asarray(v, np.float64) for v in (w_hh, h, gates, dh))
+def gru_backward(w_hh, h, gates, dh, dtype=np.float64, hook=None):
+    """-> dgates (B, T, 4H) = [dr_pre, dz_pre, dn_pre, dn_pre * r], in `dtype` throughout.
+    hook("carry", t, carry_t, dgh_t, w_hh) may replace what step t hands to step t - 1."""
+    w_hh, h, gates, dh = (np.asarray(v, dtype) for v in (w_hh, h, gates, dh))
     B, T, H = h.shape
-    dgates = np.zeros((B, T, 4 * H))
-    carry = np.zeros((B, H))
+    dgates = np.zeros((B, T, 4 * H), dtype)
+    carry = np.zeros((B, H), dtype)
     for t in range(T - 1, -1, -1):
         r, z, n, q = (gates[:, t, i * H:(i + 1) * H] for i in range(4))
-        prev = h[:, t - 1] if t > 0 else np.zeros((B, H))
+        prev = h[:, t - 1] if t > 0 else np.zeros((B, H), dtype)
         d = dh[:, t] + carry
         dn = d * (1.0 - z) * (1.0 - n * n)
         dz = d * (prev - n) * z * (1.0 - z)
         dr = dn * q * r * (1.0 - r)
         dgh = np.concatenate((dr, dz, dn * r), axis=1)
         carry = d * z + dgh @ w_hh
+        if hook is not None:
+            carry = hook("carry", t, carry, dgh, w_hh)
         dgates[:, t] = np.concatenate((dr, dz, dn, dn * r), axis=1)
     return dgates
 

@@ -3,7 +3,8 @@ against the NumPy float64 oracle (tests/_gru.py) including T = 1, instances of 4
 several GRUs per launch and the C3 length (T = 1024, H = 256); the module against fixtures the
 reference produced (tests/golden/gen_gruenc.py) and against float64 torch.nn.GRU; the batching
 of several encoders, torch.compile and the launcher's patch of the reference's SequenceEncoder.
-Tolerance: 1e-3 relative (BASELINE.json fp32 parity)."""
+Tolerance: 1e-3 relative (BASELINE.json fp32 parity); the per-step comparison with float64 across
+the launch envelope is tests/test_gpu_recurrence_envelope.py."""
 import types
 
 import numpy as np
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 from _gru import gru_backward, gru_forward
+from _rec import run_gru
 from _util import close, diff_report, load_fixture, rel_err
 
 TOL = 1e-3
@@ -26,36 +28,6 @@ def enc_mod(pkg_on_path):
 def nat(pkg_on_path):
     import mmf_native
     return mmf_native
-
-
-def _run_recurrence(nat, xproj_l, w_hh_l, b_hn_l, dh_l):
-    """Raw C-ABI forward + backward for n GRUs on cuda:0; a None entry of dh_l is passed as NULL."""
-    L = nat.lib()
-    dev = torch.device("cuda", 0)
-    n = len(xproj_l)
-    B, T, H3 = xproj_l[0].shape
-    H = H3 // 3
-    xp = [torch.from_numpy(x.astype(np.float32)).to(dev) for x in xproj_l]
-    wh = [torch.from_numpy(w.astype(np.float32)).to(dev) for w in w_hh_l]
-    bn = [torch.from_numpy(b.astype(np.float32)).to(dev) for b in b_hn_l]
-    h = [torch.empty(B, T, H, device=dev) for _ in range(n)]
-    g = [torch.empty(B, T, 4 * H, device=dev) for _ in range(n)]
-    sync = [torch.empty(L.mmf_gru_sync_bytes(B, H), dtype=torch.uint8, device=dev) for _ in range(n)]
-    tmo = torch.zeros(1, dtype=torch.int32, device=dev)
-    arr = lambda ts: nat.ptr_array([t.data_ptr() if t is not None else 0 for t in ts])  # noqa: E731
-    st = nat.stream_ptr(dev)
-    rc = L.mmf_gru_forward(n, B, T, H, arr(xp), arr(wh), arr(bn), arr(h), arr(g), arr(sync), tmo.data_ptr(), st)
-    assert rc == 0, L.mmf_last_error()
-    torch.cuda.synchronize(dev)
-    assert int(tmo.item()) == 0, "forward: inter-workgroup wait timed out"
-    dh = [torch.from_numpy(d.astype(np.float32)).to(dev) if d is not None else None for d in dh_l]
-    dg = [torch.empty(B, T, 4 * H, device=dev) for _ in range(n)]
-    rc = L.mmf_gru_backward(n, B, T, H, arr(wh), arr(h), arr(g), arr(dh), arr(dg), arr(sync), tmo.data_ptr(), st)
-    assert rc == 0, L.mmf_last_error()
-    torch.cuda.synchronize(dev)
-    assert int(tmo.item()) == 0, "backward: inter-workgroup wait timed out"
-    cpu = lambda ts: [t.cpu().double().numpy() for t in ts]  # noqa: E731
-    return cpu(h), cpu(g), cpu(dg)
 
 
 def _inputs(rng, B, T, H):
@@ -86,7 +58,7 @@ def test_recurrence_matches_oracle(nat, n, B, T, H):
         dg_last = gru_backward(w, h, g, last)
         assert np.abs(dg_last[:, 0]).max() >= 1e-3 * np.abs(dg_last).max()
         xproj_l.append(xproj); w_l.append(w); b_l.append(b_hn); dh_l.append(dh)
-    hs, gs, dgs = _run_recurrence(nat, xproj_l, w_l, b_l, dh_l)
+    hs, gs, dgs = run_gru(nat, xproj_l, w_l, b_l, dh_l)
     for i in range(n):
         h, g, dg = ref[i]
         errs = rel_err(hs[i], h), rel_err(gs[i], g), rel_err(dgs[i], dg)
@@ -104,8 +76,8 @@ def test_null_dh_equals_zeros(nat):
     ins = [_inputs(rng, B, T, H) for _ in range(n)]
     dh = rng.standard_normal((B, T, H)).astype(np.float32)
     xp, w, bn = ([v[i] for v in ins] for i in range(3))
-    _, _, with_null = _run_recurrence(nat, xp, w, bn, [dh, None])
-    _, _, with_zero = _run_recurrence(nat, xp, w, bn, [dh, np.zeros_like(dh)])
+    _, _, with_null = run_gru(nat, xp, w, bn, [dh, None])
+    _, _, with_zero = run_gru(nat, xp, w, bn, [dh, np.zeros_like(dh)])
     assert np.array_equal(with_null[0], with_zero[0]) and np.array_equal(with_null[1], with_zero[1])
     assert not with_null[1].any() and with_null[0].any()
 
@@ -121,7 +93,7 @@ def test_recurrence_c3_length(nat):
     dh_l = [np.zeros((B, T, H), np.float32) for _ in range(n)]
     for d in dh_l:
         d[:, -1] = rng.standard_normal((B, H))       # only the final state feeds the projection
-    hs, gs, dgs = _run_recurrence(nat, xp, w, bn, dh_l)
+    hs, gs, dgs = run_gru(nat, xp, w, bn, dh_l)
     for i in (0, 3):
         h, g = gru_forward(xp[i], w[i], bn[i])
         dg = gru_backward(w[i], h, g, dh_l[i])

@@ -3,13 +3,13 @@ src/encoders.py:34-166): the module against fixtures the reference produced
 (tests/golden/gen_golden.py, SEQENC_CASES), the raw C-ABI recurrence against
 the CPU oracle (oracle/lstm_cpu.py) including T = 1, batch instances of <= 4 rows,
 several LSTMs per launch and a NULL dh, and the C3 shape (T = 1024, H = 256) at full length.
-Tolerance: 1e-3 relative (BASELINE.json fp32 parity)."""
-import ctypes
-
+Tolerance: 1e-3 relative (BASELINE.json fp32 parity); the per-step comparison with float64 across
+the launch envelope is tests/test_gpu_recurrence_envelope.py."""
 import numpy as np
 import pytest
 import torch
 
+from _rec import run_lstm
 from _util import close, load_fixture, rel_err
 from cases import SEQENC_CASES, seqenc_inputs, seqenc_state
 
@@ -51,39 +51,18 @@ def test_lstm_limits_cpu(nat):
     L = nat.lib()
     assert L.mmf_lstm_sync_bytes(3, 256) == 2 * 4 * 3 * 256 * 8
     null = nat.ptr_array([0])
-    for n, B, T, H in ((1, 1, 4, 96), (1, 1, 4, 320), (9, 1, 4, 64), (4, 33, 4, 64), (1, 0, 4, 64)):
+    # (8, 17, 4, 64): 8 x ceil(17 / 4) = 40 instances, over the 32 a launch holds
+    for n, B, T, H in ((1, 1, 4, 96), (1, 1, 4, 320), (9, 1, 4, 64), (4, 33, 4, 64), (1, 0, 4, 64), (8, 17, 4, 64)):
         rc = L.mmf_lstm_forward(n, B, T, H, null, null, null, null, null, null, None, None)
         assert rc == 2, (n, B, T, H)
         rc = L.mmf_lstm_backward(n, B, T, H, null, null, null, null, null, null, None, None)
         assert rc == 2, (n, B, T, H)
-
-
-def _run_recurrence(nat, enc_mod, xproj_l, w_hh_l, dh_l):
-    """Raw C-ABI forward + backward for n LSTMs on cuda:0; a None entry of dh_l is passed as NULL."""
-    L = nat.lib()
-    dev = torch.device("cuda", 0)
-    n = len(xproj_l)
-    B, T, H4 = xproj_l[0].shape
-    H = H4 // 4
-    xp = [torch.from_numpy(x.astype(np.float32)).to(dev) for x in xproj_l]
-    wh = [torch.from_numpy(w.astype(np.float32)).to(dev) for w in w_hh_l]
-    h = [torch.empty(B, T, H, device=dev) for _ in range(n)]
-    c = [torch.empty(B, T, H, device=dev) for _ in range(n)]
-    g = [torch.empty(B, T, 4 * H, device=dev) for _ in range(n)]
-    sync = [torch.empty(L.mmf_lstm_sync_bytes(B, H), dtype=torch.uint8, device=dev) for _ in range(n)]
-    tmo = torch.zeros(1, dtype=torch.int32, device=dev)
-    arr = lambda ts: nat.ptr_array([t.data_ptr() if t is not None else 0 for t in ts])  # noqa: E731
-    st = nat.stream_ptr(dev)
-    rc = L.mmf_lstm_forward(n, B, T, H, arr(xp), arr(wh), arr(h), arr(c), arr(g), arr(sync), tmo.data_ptr(), st)
-    assert rc == 0, nat.lib().mmf_last_error()
-    dh = [torch.from_numpy(d.astype(np.float32)).to(dev) if d is not None else None for d in dh_l]
-    dg = [torch.empty(B, T, 4 * H, device=dev) for _ in range(n)]
-    rc = L.mmf_lstm_backward(n, B, T, H, arr(wh), arr(c), arr(g), arr(dh), arr(dg), arr(sync), tmo.data_ptr(), st)
-    assert rc == 0, nat.lib().mmf_last_error()
-    torch.cuda.synchronize(dev)
-    assert int(tmo.item()) == 0, "inter-workgroup wait timed out"
-    cpu = lambda ts: [t.cpu().double().numpy() for t in ts]  # noqa: E731
-    return cpu(h), cpu(c), cpu(g), cpu(dg)
+    # (8, 16, 4, 64) is 32 instances and passes the plan: refused only for the missing timeout word
+    # (MMF_EINVAL, the plan's last check), still before the device is touched
+    rc = L.mmf_lstm_forward(8, 16, 4, 64, null, null, null, null, null, null, None, None)
+    assert rc == 1 and b"timeout word" in L.mmf_last_error(), (rc, L.mmf_last_error())
+    rc = L.mmf_lstm_backward(8, 16, 4, 64, null, null, null, null, null, null, None, None)
+    assert rc == 1 and b"timeout word" in L.mmf_last_error(), (rc, L.mmf_last_error())
 
 
 @pytest.mark.gpu
@@ -102,7 +81,7 @@ def test_recurrence_matches_oracle(nat, enc_mod, n, B, T, H):
                                np.zeros(4 * H, np.float32))
         ref.append((h, c, g, lstm_backward(w, c, g, dh)))
         xproj_l.append(xproj); w_l.append(w); dh_l.append(dh)
-    hs, cs, gs, dgs = _run_recurrence(nat, enc_mod, xproj_l, w_l, dh_l)
+    hs, cs, gs, dgs = run_lstm(nat, xproj_l, w_l, dh_l)
     for i in range(n):
         h, c, g, dg = ref[i]
         assert rel_err(torch.from_numpy(hs[i]), h) <= TOL, i
@@ -120,8 +99,8 @@ def test_null_dh_equals_zeros(nat, enc_mod):
     xp = [rng.standard_normal((B, T, 4 * H)).astype(np.float32) for _ in range(n)]
     w = [rng.uniform(-bound, bound, size=(4 * H, H)).astype(np.float32) for _ in range(n)]
     dh = rng.standard_normal((B, T, H)).astype(np.float32)
-    with_null = _run_recurrence(nat, enc_mod, xp, w, [dh, None])[3]
-    with_zero = _run_recurrence(nat, enc_mod, xp, w, [dh, np.zeros_like(dh)])[3]
+    with_null = run_lstm(nat, xp, w, [dh, None])[3]
+    with_zero = run_lstm(nat, xp, w, [dh, np.zeros_like(dh)])[3]
     assert np.array_equal(with_null[0], with_zero[0]) and np.array_equal(with_null[1], with_zero[1])
     assert not with_null[1].any() and with_null[0].any()
 
@@ -138,7 +117,7 @@ def test_recurrence_c3_length(nat, enc_mod):
     dh_l = [np.zeros((B, T, H), np.float32) for _ in range(n)]
     for d in dh_l:
         d[:, -1] = rng.standard_normal((B, H))       # only the final state feeds the projection
-    hs, cs, gs, dgs = _run_recurrence(nat, enc_mod, xproj_l, w_l, dh_l)
+    hs, cs, gs, dgs = run_lstm(nat, xproj_l, w_l, dh_l)
     eye, z = np.eye(4 * H, dtype=np.float32), np.zeros(4 * H, np.float32)
     for i in (0, 3):
         h, c, g = lstm_forward(xproj_l[i], eye, w_l[i], z, z)

@@ -92,7 +92,8 @@ def test_gru_limits(nat):
     assert L.mmf_gru_sync_bytes(3, 256) == 2 * 4 * 3 * 256 * 8
     assert L.mmf_gru_sync_bytes(3, 256) == L.mmf_lstm_sync_bytes(3, 256)
     null = nat.ptr_array([0])
-    for n, B, T, H in ((1, 1, 4, 96), (1, 1, 4, 320), (9, 1, 4, 64), (4, 33, 4, 64), (1, 0, 4, 64)):
+    # (8, 17, 4, 64): 8 x ceil(17 / 4) = 40 instances, over the 32 a launch holds
+    for n, B, T, H in ((1, 1, 4, 96), (1, 1, 4, 320), (9, 1, 4, 64), (4, 33, 4, 64), (1, 0, 4, 64), (8, 17, 4, 64)):
         rc = L.mmf_gru_forward(n, B, T, H, null, null, null, null, null, null, None, None)
         assert rc == 2, (n, B, T, H)
         rc = L.mmf_gru_backward(n, B, T, H, null, null, null, null, null, null, None, None)
@@ -100,6 +101,11 @@ def test_gru_limits(nat):
     # a valid shape without a timeout word: MMF_EINVAL, still before the device
     assert L.mmf_gru_forward(1, 1, 4, 64, null, null, null, null, null, null, None, None) == 1
     assert L.mmf_gru_backward(1, 1, 4, 64, null, null, null, null, null, null, None, None) == 1
+    # (8, 16, 4, 64) is 32 instances and passes the plan up to that same last check
+    rc = L.mmf_gru_forward(8, 16, 4, 64, null, null, null, null, null, null, None, None)
+    assert rc == 1 and b"timeout word" in L.mmf_last_error(), (rc, L.mmf_last_error())
+    rc = L.mmf_gru_backward(8, 16, 4, 64, null, null, null, null, null, null, None, None)
+    assert rc == 1 and b"timeout word" in L.mmf_last_error(), (rc, L.mmf_last_error())
 
 
 def test_fake_kernels(enc_mod):
