@@ -30,18 +30,17 @@ costs by itself).
 """
 import functools
 
-import numpy as np
 import pytest
 import torch
 
+import _seqstep
 from _philox import mask_provider
-from _util import (EPS32, bf16_matmul_mode, close_sliced, device_relu_gates, sliced_ratio, sliced_report,
-                   zero_grad_bound)
+from _seqstep import OFFSET, SEED
+from _util import bf16_matmul_mode
 from cases import HybridCase, hybrid_inputs, hybrid_state
 from test_gpu_attn_headdims import C, CAP
 
 pytestmark = pytest.mark.gpu
-SEED, OFFSET = 0x2468_ACE0_1357, 3
 
 POOL_CASES = [
     # attn_pool_fwd_kernel<64>, attn_pool_bwd_dq_kernel<64>, attn_pool_bwd_dk_kernel<64>, padded
@@ -76,10 +75,6 @@ EXPECT = {   # name prefixes of the instantiations each case exists for
 }
 
 
-def case_labels(case):
-    return torch.from_numpy(np.random.default_rng(case.seed + 31337).integers(0, case.classes, case.batch))
-
-
 @pytest.fixture(scope="module")
 def env(pkg_on_path):
     if not torch.cuda.is_available():
@@ -92,29 +87,7 @@ def env(pkg_on_path):
 
 
 def build_model(fusion, case):
-    model = fusion.HybridFusion({m: case.dims[m] for m in case.names}, hidden_dim=case.hidden,
-                                num_classes=case.classes, num_heads=case.heads, dropout=DROPOUT[case.name])
-    sd = hybrid_state(case.names, case.dims, case.hidden, case.classes, case.seed)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    return model.cuda(), sd
-
-
-def oracle_step(case, sd, dtype, seed, offset, taps=None, relu_gate=None):
-    """forward -> CE(label_smoothing 0.05) -> backward of the oracle under the replayed masks:
-    {logits, loss, dx/<m>, <parameter name>}."""
-    from oracle.hybrid_cpu import cross_entropy_ls, hybrid_forward
-    p = DROPOUT[case.name]
-    feats_np, mask_np, _ = hybrid_inputs(case)
-    params = {k: torch.from_numpy(v).to(dtype).requires_grad_(True) for k, v in sd.items()}
-    xs = {m: torch.from_numpy(v).to(dtype).requires_grad_(True) for m, v in feats_np.items()}
-    logits, _ = hybrid_forward(params, case.names, xs, torch.from_numpy(mask_np).to(dtype), case.heads, p=p,
-                               train=True, gen=mask_provider(seed, offset, p), taps=taps, relu_gate=relu_gate)
-    loss = cross_entropy_ls(logits, case_labels(case))
-    loss.backward()
-    out = {"logits": logits.detach(), "loss": loss.detach()}
-    out.update({f"dx/{m}": xs[m].grad for m in case.names})
-    out.update({n: p_.grad for n, p_ in params.items()})
-    return out
+    return _seqstep.build_model(fusion, case, DROPOUT[case.name])
 
 
 @pytest.mark.parametrize("name", [c.name for c in POOL_CASES])
@@ -124,16 +97,7 @@ def test_hybrid_step_vs_fp64(env, name):
     prev = torch.get_float32_matmul_precision()
     torch.set_float32_matmul_precision("highest")
     try:
-        model, sd = build_model(fusion, case)
-        feats_np, mask_np, _ = hybrid_inputs(case)
-        step = train_step.HybridTrainStep(model, [torch.from_numpy(feats_np[m]).cuda() for m in case.names],
-                                          torch.from_numpy(mask_np).cuda(), case_labels(case).cuda())
-        step.rng.copy_(torch.tensor([SEED, OFFSET], dtype=torch.int64))
-        seed, offset = (int(v) for v in step.rng.tolist())
-        nat.profile_begin()
-        step.forward_backward()
-        torch.cuda.synchronize()
-        _, launches = nat.profile_end()
+        step, sd, got, launches, seed, offset = _seqstep.device_step(nat, fusion, train_step, case, DROPOUT[name])
     finally:
         torch.set_float32_matmul_precision(prev)
     ran = [k for _, k, *_ in launches]
@@ -141,39 +105,8 @@ def test_hybrid_step_vs_fp64(env, name):
     for want in EXPECT[name]:
         assert any(k.startswith(want) for k in ran), (want, sorted(set(ran)))
 
-    got = {"logits": step.logits.cpu(), "loss": step.loss.reshape(()).cpu()}
-    got.update({f"dx/{m}": step.dx[i].cpu() for i, m in enumerate(case.names)})
-    got.update({n: g.cpu() for n, g in step.named_grads().items()})
-
-    # the device's ReLU decisions for the pre-activations within rounding of zero
-    dev_acts = {m: step.saved_activation("proj", i).cpu() for i, m in enumerate(case.names)}
-    dev_acts["cls"] = step.saved_activation("cls_hidden").cpu()
-    taps = {}
-    oracle_step(case, sd, torch.float64, seed, offset, taps=taps)
-    wts = {m: torch.from_numpy(sd[f"projections.{m}.0.weight"]) for m in case.names}
-    wts["cls"] = torch.from_numpy(sd["classifier.0.weight"])
-    gates, counts = device_relu_gates(taps, wts, dev_acts)
-    print(f"HEADDIMS {name} pre-activations in the band: {counts}")
-    ref64 = oracle_step(case, sd, torch.float64, seed, offset, relu_gate=gates)
-    ref32 = oracle_step(case, sd, torch.float32, seed, offset, relu_gate=gates)
-
-    assert set(got) == set(ref64), (sorted(got), sorted(ref64))
-    scale = max(float(ref64[k].abs().max()) for k in ref64 if k not in ("logits", "loss"))
-    bad = []
-    for key in ref64:
-        if key.endswith("key_proj.bias"):
-            g, own = float(got[key].abs().max()), float(ref32[key].abs().max())
-            bound = zero_grad_bound(ref32[key], scale, C)
-            print(f"HEADDIMS {name} {key}: max|got| {g:.3e}, fp32 oracle {own:.3e}, 2^-24 S {EPS32 * scale:.3e}, "
-                  f"ratio {g / max(own, EPS32 * scale):.2f}")
-            if not g <= bound:
-                bad.append(f"{key}: max|got| {g:.3e} > {bound:.3e}")
-            continue
-        sdim = 0 if key == "logits" or key.startswith("dx/") else None
-        ratio, e_dev = sliced_ratio(got[key], ref64[key], ref32[key], slice_dim=sdim)
-        print(f"HEADDIMS {name} {key}: ratio {ratio:.2f}, e_dev {e_dev:.3e}")
-        if not close_sliced(got[key], ref64[key], ref32[key], slice_dim=sdim, c=C, cap=CAP):
-            bad.append(f"{key}: " + sliced_report(got[key], ref64[key], ref32[key], slice_dim=sdim, c=C, cap=CAP))
+    ref64, ref32 = _seqstep.gated_references(step, case, sd, seed, offset, DROPOUT[name], f"HEADDIMS {name}")
+    bad, _, _ = _seqstep.compare(got, ref64, ref32, f"HEADDIMS {name}", C, CAP)
     assert not bad, "\n".join(bad)
 
 
