@@ -431,6 +431,63 @@ int mmf_conv_encoder_backward(int32_t batch, int32_t steps, int32_t in_dim, int3
                               float* dbeta2, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------
+ * Transformer sequence encoder's layer stack and pool (SequenceEncoder 'transformer',
+ * src/encoders.py:99-111 / 177-206): `layers` post-norm nn.TransformerEncoderLayer(d_model = hidden,
+ * nhead = 4, dim_feedforward = ffn, ReLU, batch_first) with src_key_padding_mask t >= lengths[b],
+ * then the mean over the valid steps:
+ *   per layer  a = MHA(x) (one QKV GEMM, flash attention over the valid keys, out_proj);
+ *              y1 = LayerNorm1(x + Drop(a)); f = linear2(Drop(ReLU(linear1(y1))));
+ *              x' = LayerNorm2(y1 + Drop(f))
+ *   pooled[b] = sum_{t < len_b} x[b, t] / max(len_b, 1)
+ * x (B, T, hidden) is the output of the encoder's input_projection; lengths int64 (B) on the device
+ * or NULL (every step valid); a length above T counts as T, below 0 as 0.  A sample of length 0
+ * gets pooled = 0 and zero gradients (torch returns NaN there: its softmax over no key is 0 / 0).
+ * Parameters per layer in torch's layout: in_proj (3 hidden, hidden), out_proj (hidden, hidden),
+ * linear1 (ffn, hidden), linear2 (hidden, ffn), the two LayerNorms' weight / bias (hidden).
+ * LayerNorm: mean, then the biased variance of the centred values, rstd = 1 / sqrt(var + eps); the
+ * forward saves z = x + r and (mean, rstd) per row.  Dropout (training != 0 and dropout > 0) draws
+ * the call's Philox snapshot at sites 0x500 + 4 layer + {0 attention probabilities, 1 out_proj,
+ * 2 linear1's activation, 3 linear2}, element index row * width + column (attention: ((b heads + h)
+ * T + q) T + k); rng_state (needed only then) is snapshot into `saved` and advanced by one.
+ * Backward of sum(pooled * dpooled): every parameter gradient is WRITTEN; dx (B, T, hidden) may be
+ * NULL.  dx rows at t >= len_b are exactly 0.  Every cross-workgroup dependency is a kernel
+ * boundary (no atomics, no waits); reductions run in a fixed order: reruns are bit-identical.
+ * The matmuls are fp32 MFMA at every matmul-precision setting.
+ * Limits (MMF_ELIMIT, checked before anything touches the device): hidden % 4 == 0 and 4 <= hidden
+ * <= 256 (4 heads, head_dim <= 64), 1 <= ffn <= 8192, 1 <= layers <= 8, batch >= 1, steps >= 1,
+ * batch * steps <= 2^24; dropout outside [0, 1) or eps < 0 is MMF_EINVAL.
+ * The size queries return 0 (with an error message) outside the limits; the forward's workspace is
+ * mmf_transformer_encoder_workspace_bytes(..., backward = 0), the backward's (..., 1).
+ * ------------------------------------------------------------------- */
+#define MMF_TRANSFORMER_MAX_LAYERS 8
+typedef struct mmf_transformer_desc {
+  int32_t batch, steps, hidden, ffn, layers;
+  int32_t training;
+  float dropout, eps;
+} mmf_transformer_desc;
+typedef struct mmf_transformer_layer {
+  const float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b;
+  const float *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+  const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} mmf_transformer_layer;
+typedef struct mmf_transformer_layer_grad {
+  float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b;
+  float *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+  float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} mmf_transformer_layer_grad;
+size_t mmf_transformer_encoder_saved_bytes(int32_t batch, int32_t steps, int32_t hidden, int32_t ffn,
+                                           int32_t layers);
+size_t mmf_transformer_encoder_workspace_bytes(int32_t batch, int32_t steps, int32_t hidden, int32_t ffn,
+                                               int32_t layers, int32_t backward);
+int mmf_transformer_encoder_forward(const mmf_transformer_desc* desc, const mmf_transformer_layer* params,
+                                    const float* x, const int64_t* lengths, uint64_t* rng_state, void* saved,
+                                    float* pooled, void* workspace, void* stream);
+int mmf_transformer_encoder_backward(const mmf_transformer_desc* desc, const mmf_transformer_layer* params,
+                                     const float* x, const int64_t* lengths, const void* saved,
+                                     const float* dpooled, void* workspace,
+                                     const mmf_transformer_layer_grad* grads, float* dx, void* stream);
+
+/* ---------------------------------------------------------------------
  * Training-step helpers used by the data-parallel step (not part of the
  * reference interface; the reference uses torch.optim.AdamW via Lightning,
  * src/train.py:374-414).

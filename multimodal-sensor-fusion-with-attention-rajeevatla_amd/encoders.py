@@ -27,8 +27,9 @@ time-parallel input projection and weight gradients are rocBLAS GEMMs.
 launches.  The recurrence's workgroups wait on each other: the library refuses
 a grid that cannot be co-resident, every launch gets a fresh timeout word, and
 a wait that gives up poisons its outputs with NaN; ``lstm_timed_out()`` /
-``check_lstm_timeouts()`` report such launches (one stream sync per check).  The 'transformer'
-encoder type is not on the path and raises NotImplementedError.
+``check_lstm_timeouts()`` report such launches (one stream sync per check).  SequenceEncoder(...,
+encoder_type="transformer") itself raises NotImplementedError; TransformerSequenceEncoder (below)
+serves that type.
 
 GRUSequenceEncoder mirrors the reference's 'gru' branch (src/encoders.py:77-85, 135-166): the same
 attributes, construction order and state_dict keys (rnn.*, projection.*), the same forward(sequence,
@@ -54,6 +55,19 @@ torch.get_float32_matmul_precision() setting (more precise than "high" / "medium
 SequenceEncoder(..., encoder_type="cnn") itself still raises NotImplementedError, naming
 ConvSequenceEncoder; ``build_encoder`` (the reference's factory, src/encoders.py:400-451) returns
 the right class for a modality and its config.
+
+TransformerSequenceEncoder mirrors the reference's 'transformer' branch (src/encoders.py:99-111,
+177-206: input_projection -> post-norm nn.TransformerEncoder (4 heads, ReLU, dim_feedforward 2048)
+with the key padding mask t >= lengths[b] -> mean over the valid steps -> dropout -> Linear), with
+the reference's state_dict keys and initialisation.  ``transformer`` holds the parameters; the
+layer stack and the pool run forward and backward behind mmf_transformer_encoder_forward /
+_backward (csrc/transformer.hip: the library's fp32 MFMA GEMMs and flash attention chained through
+residual + LayerNorm, masked-mean-pool and their backward kernels; statistics from centred values,
+in-kernel Philox dropout at four sites per layer, fixed-order reductions, no inter-workgroup
+waits).  input_projection, the final dropout and projection stay nn.Linear / nn.Dropout.  A sample
+of length 0 gets a zero pooled vector and zero gradients (the reference returns NaN there).
+SequenceEncoder(..., encoder_type="transformer") itself still raises NotImplementedError, naming
+TransformerSequenceEncoder; ``build_encoder`` returns it for that type.
 """
 
 from __future__ import annotations
@@ -408,8 +422,9 @@ class SequenceEncoder(nn.Module):
             raise NotImplementedError("encoder_type 'gru' is served by GRUSequenceEncoder (build_encoder returns it "
                                       "for encoder_type='gru'), not by SequenceEncoder")
         elif encoder_type == "transformer":
-            raise NotImplementedError("encoder_type 'transformer' is not on the MI355X path (build_encoder returns "
-                                      "the encoders that are)")
+            raise NotImplementedError("encoder_type 'transformer' is not on the MI355X path as a SequenceEncoder: it "
+                                      "is served by TransformerSequenceEncoder (build_encoder returns it for "
+                                      "encoder_type='transformer')")
         else:
             raise ValueError(f"Unknown encoder type: {encoder_type}")
 
@@ -564,13 +579,114 @@ class ConvSequenceEncoder(nn.Module):
         return self.projection(self.dropout_layer(pooled))
 
 
+class TransformerSequenceEncoder(nn.Module):
+    """The reference SequenceEncoder's 'transformer' branch (src/encoders.py:99-111, 177-206) on the HIP
+    path: the same attributes, construction order (the same seed gives the same weights) and
+    state_dict (input_projection.*, transformer.layers.{k}.*, projection.*).  ``transformer`` is the
+    reference's nn.TransformerEncoder and only holds the parameters; the layer stack, the key padding
+    mask from ``lengths`` and the mean over the valid steps run in csrc/transformer.hip.  A sample of
+    length 0 encodes as projection(0) with zero gradients where the reference gives NaN."""
+
+    encoder_type: str
+    hidden_dim: int
+    output_dim: int
+    rnn: Optional[nn.Module]
+    conv_net: Optional[nn.Module]
+    pool: Optional[nn.Module]
+    input_projection: Optional[nn.Linear]
+    transformer: Optional[nn.TransformerEncoder]
+    projection: nn.Module
+
+    def __init__(self, input_dim: int, hidden_dim: int = 256, output_dim: int = 128, num_layers: int = 2,
+                 dropout: float = 0.1):
+        super().__init__()
+        cast_self = cast(Any, self)
+        cast_self.encoder_type = "transformer"
+        cast_self.hidden_dim = hidden_dim
+        cast_self.output_dim = output_dim
+        self.dropout_layer = nn.Dropout(dropout)
+        cast_self.rnn = None
+        cast_self.conv_net = None
+        cast_self.pool = None
+        cast_self.input_projection = None
+        cast_self.transformer = None
+        self.projection = nn.Identity()   # (registered first, as in the reference: the module order)
+        cast_self.input_projection = nn.Linear(input_dim, hidden_dim)
+        nhead = 4 if hidden_dim % 4 == 0 else 1
+        encoder_layer = nn.TransformerEncoderLayer(d_model=hidden_dim, nhead=nhead, dropout=dropout, batch_first=True)
+        cast_self.transformer = nn.TransformerEncoder(encoder_layer, num_layers=num_layers)
+        self.projection = nn.Linear(hidden_dim, output_dim)
+        from attention import _new_rng_state   # the device Philox state of one module; torch's RNG untouched
+        self.register_buffer("_rng_state", _new_rng_state(), persistent=False)
+
+    def _stack(self):
+        """(layers, dropout p, LayerNorm eps) when ``transformer`` is still the structure the kernels
+        implement: post-norm ReLU layers with biases, 4 heads, batch_first, no final norm."""
+        net = self.transformer
+        layers = list(net.layers) if isinstance(net, nn.TransformerEncoder) else []
+        ok = len(layers) >= 1 and net.norm is None
+        p = eps = None
+        for lyr in layers:
+            ok = ok and isinstance(lyr, nn.TransformerEncoderLayer)
+            if not ok:
+                break
+            att = lyr.self_attn
+            act = lyr.activation
+            relu = act is torch.nn.functional.relu or act is torch.relu or isinstance(act, nn.ReLU)
+            ok = ok and not lyr.norm_first and relu
+            ok = ok and isinstance(att, nn.MultiheadAttention) and att.batch_first and att._qkv_same_embed_dim
+            ok = ok and att.num_heads == 4 and att.in_proj_bias is not None and att.out_proj.bias is not None
+            ok = ok and att.bias_k is None and att.bias_v is None and not att.add_zero_attn
+            ok = ok and lyr.linear1.bias is not None and lyr.linear2.bias is not None
+            ok = ok and isinstance(lyr.norm1, nn.LayerNorm) and isinstance(lyr.norm2, nn.LayerNorm)
+            ok = ok and lyr.norm1.elementwise_affine and lyr.norm2.elementwise_affine
+            ok = ok and lyr.norm1.bias is not None and lyr.norm2.bias is not None
+            if not ok:
+                break
+            ps = {float(att.dropout), float(lyr.dropout.p), float(lyr.dropout1.p), float(lyr.dropout2.p)}
+            es = {float(lyr.norm1.eps), float(lyr.norm2.eps)}
+            ok = ok and len(ps) == 1 and len(es) == 1
+            ok = ok and (p is None or p == next(iter(ps))) and (eps is None or eps == next(iter(es)))
+            p, eps = next(iter(ps)), next(iter(es))
+            ok = ok and lyr.linear1.in_features == lyr.linear2.out_features == att.embed_dim == self.hidden_dim
+            ok = ok and lyr.linear1.out_features == lyr.linear2.in_features
+            ok = ok and lyr.linear1.out_features == layers[0].linear1.out_features
+        if not ok:
+            raise NotImplementedError("TransformerSequenceEncoder: the HIP path implements a stack of post-norm "
+                                      "nn.TransformerEncoderLayer (4 heads, ReLU, biases, batch_first, equal dropout "
+                                      "and eps, no final norm) only (there is no torch fallback)")
+        return layers, p, eps
+
+    def forward(self, sequence: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if sequence.dim() != 3:
+            raise ValueError(f"Expected 3D input sequence, got shape {sequence.shape}")
+        if self.input_projection is None or self.transformer is None:
+            raise RuntimeError("Transformer modules not initialized.")
+        layers, p, eps = self._stack()
+        _nat.require_device(sequence, "TransformerSequenceEncoder input")
+        x = _nat.f32c(self.input_projection(_nat.f32c(sequence)))
+        lens = None
+        if lengths is not None:
+            lens = lengths.to(device=x.device, dtype=torch.int64).contiguous()
+        params: List[torch.Tensor] = []
+        for lyr in layers:
+            att = lyr.self_attn
+            params += [att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias,
+                       lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, lyr.linear2.bias,
+                       lyr.norm1.weight, lyr.norm1.bias, lyr.norm2.weight, lyr.norm2.bias]
+        pooled, _saved, rng_next = torch.ops.mmfusion.transformer_encoder_fwd(
+            x, lens, self._rng_state, params, bool(self.transformer.training), float(p), float(eps))
+        self._rng_state.copy_(rng_next)     # the device Philox stream advanced by one call
+        return self.projection(self.dropout_layer(pooled))
+
+
 def build_encoder(modality: str, input_dim: int, output_dim: int,
                   encoder_config: Optional[Dict[str, Any]] = None) -> nn.Module:
     """The reference's factory (src/encoders.py:400-451): the config's ``type`` ('frame' /
     'sequence' / 'mlp') decides, else the modality name (video / frames -> FrameEncoder; imu /
     audio / mocap / accelerometer / imu_* -> sequence).  A sequence encoder with
-    ``encoder_type == 'cnn'`` is a ConvSequenceEncoder, with 'gru' a GRUSequenceEncoder, any other a
-    SequenceEncoder.  The MLP
+    ``encoder_type == 'cnn'`` is a ConvSequenceEncoder, with 'gru' a GRUSequenceEncoder, with
+    'transformer' a TransformerSequenceEncoder, any other a SequenceEncoder.  The MLP
     encoder (type 'mlp' and unknown modalities) is not on the MI355X path."""
     config: Dict[str, Any] = dict(encoder_config) if encoder_config else {}
     kind = config.pop("type", None)
@@ -585,6 +701,9 @@ def build_encoder(modality: str, input_dim: int, output_dim: int,
         if config.get("encoder_type", "lstm") == "gru":
             config.pop("encoder_type")
             return GRUSequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
+        if config.get("encoder_type", "lstm") == "transformer":
+            config.pop("encoder_type")
+            return TransformerSequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
         return SequenceEncoder(input_dim=input_dim, output_dim=output_dim, **config)
     # SimpleMLPEncoder (src/encoders.py:339-397) serves config 1's EarlyFusion CPU plumbing only
     raise NotImplementedError(f"encoder for modality '{modality}' ({kind or 'mlp'}) is not on the MI355X path")

@@ -101,7 +101,8 @@ class MultimodalFusionModel(nn.Module):
             ec = dict(mc.get("encoders", {}).get(m, {}))
             in_dim = int(ec.pop("input_dim", 64))
             # FrameEncoder / SequenceEncoder ('lstm') / GRUSequenceEncoder ('gru') / ConvSequenceEncoder
-            # ('cnn'); the 'transformer' type, the MLP encoder and unknown modalities raise NotImplementedError
+            # ('cnn') / TransformerSequenceEncoder ('transformer'); the MLP encoder and unknown modalities
+            # raise NotImplementedError
             encs[m] = build_encoder(m, in_dim, out_dim, ec)
         fusion = build_fusion_model(mc.get("fusion_type", "hybrid"), {m: out_dim for m in encs},
                                     int(ds.get("num_classes", 11)), hidden_dim=int(mc["hidden_dim"]),

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "mmf_mc_reduce", "mmf_hybrid_mc_forward", "mmf_temperature_nll_workspace_bytes", "mmf_temperature_nll",
     "mmf_uncertainty_fusion_forward", "mmf_uncertainty_fusion_backward",
     "mmf_conv_encoder_workspace_bytes", "mmf_conv_encoder_forward", "mmf_conv_encoder_backward",
+    "mmf_transformer_encoder_saved_bytes", "mmf_transformer_encoder_workspace_bytes",
+    "mmf_transformer_encoder_forward", "mmf_transformer_encoder_backward",
 )
 
 
@@ -110,6 +112,25 @@ class CmaParams(ctypes.Structure):
 
 
 CmaGrads = CmaParams
+
+TRANSFORMER_MAX_LAYERS = 8
+# mmf_transformer_layer's pointers, in order: torch's parameter order of one nn.TransformerEncoderLayer
+TRANSFORMER_LAYER_FIELDS = ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "linear1_w", "linear1_b",
+                            "linear2_w", "linear2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")
+
+
+class TransformerDesc(ctypes.Structure):
+    _fields_ = [
+        ("batch", c_int32), ("steps", c_int32), ("hidden", c_int32), ("ffn", c_int32), ("layers", c_int32),
+        ("training", c_int32), ("dropout", c_float), ("eps", c_float),
+    ]
+
+
+class TransformerLayer(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TRANSFORMER_LAYER_FIELDS]
+
+
+TransformerLayerGrad = TransformerLayer   # identical layout
 
 _LIB: Optional[ctypes.CDLL] = None
 
@@ -239,6 +260,16 @@ def lib() -> ctypes.CDLL:
     L.mmf_conv_encoder_forward.restype = c_int32
     L.mmf_conv_encoder_backward.argtypes = [c_int32] * 5 + [vp] * 19
     L.mmf_conv_encoder_backward.restype = c_int32
+    L.mmf_transformer_encoder_saved_bytes.argtypes = [c_int32] * 5
+    L.mmf_transformer_encoder_saved_bytes.restype = sz
+    L.mmf_transformer_encoder_workspace_bytes.argtypes = [c_int32] * 6
+    L.mmf_transformer_encoder_workspace_bytes.restype = sz
+    # (desc, layers, x, lengths, rng_state, saved, pooled, workspace, stream)
+    L.mmf_transformer_encoder_forward.argtypes = [POINTER(TransformerDesc), vp] + [vp] * 7
+    L.mmf_transformer_encoder_forward.restype = c_int32
+    # (desc, layers, x, lengths, saved, dpooled, workspace, layer grads, dx, stream)
+    L.mmf_transformer_encoder_backward.argtypes = [POINTER(TransformerDesc), vp] + [vp] * 8
+    L.mmf_transformer_encoder_backward.restype = c_int32
     L.mmf_last_error.argtypes = []
     L.mmf_last_error.restype = ctypes.c_char_p
     L.mmf_version.argtypes = []

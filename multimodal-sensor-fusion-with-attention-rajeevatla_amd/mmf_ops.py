@@ -29,6 +29,7 @@ Operators (csrc entry point, reference interface):
   temperature_nll                  mmf_temperature_nll               src/uncertainty.py:431-435
   uncertainty_fusion_fwd / _bwd    mmf_uncertainty_fusion_*          src/uncertainty.py:305-362
   conv_encoder_fwd / _bwd          mmf_conv_encoder_forward / _backward  src/encoders.py:87-97, 168-175
+  transformer_encoder_fwd / _bwd   mmf_transformer_encoder_forward / _backward  src/encoders.py:99-111, 177-206
 """
 
 from __future__ import annotations
@@ -1183,3 +1184,110 @@ def _ce_conv_backward(ctx, dpooled, _dy1, _dy2, _ds1, _ds2):
 
 
 conv_encoder_fwd.register_autograd(_ce_conv_backward, setup_context=_ce_conv_setup)
+
+
+# ============================================================================ Transformer sequence encoder (layer stack + pool)
+# params: 12 tensors per layer, mmf_native.TRANSFORMER_LAYER_FIELDS order (torch's parameter order of
+# an nn.TransformerEncoderLayer): in_proj weight / bias, out_proj, linear1, linear2, norm1, norm2
+_TDESC: Dict[tuple, "_nat.TransformerDesc"] = {}
+_TPL = len(_nat.TRANSFORMER_LAYER_FIELDS)
+
+
+def _transformer_desc(x: Tensor, params: Sequence[Tensor], training: bool, dropout: float,
+                      eps: float) -> "_nat.TransformerDesc":
+    if len(params) == 0 or len(params) % _TPL != 0:
+        raise ValueError(f"transformer_encoder: expected {_TPL} parameters per layer, got {len(params)}")
+    B, T, H = x.shape
+    key = (B, T, H, int(params[4].shape[0]), len(params) // _TPL, int(training), float(dropout), float(eps))
+    d = _TDESC.get(key)
+    if d is None:
+        d = _TDESC[key] = _nat.TransformerDesc(*key)
+    return d
+
+
+def _transformer_layers(ptrs: Sequence[Optional[int]]):
+    """The mmf_transformer_layer (or _grad) array of these addresses: one struct of 12 pointers per layer."""
+    arr = (_nat.TransformerLayer * (len(ptrs) // _TPL))()
+    flat = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
+    for i, p in enumerate(ptrs):
+        flat[i] = p
+    return arr
+
+
+@torch.library.custom_op("mmfusion::transformer_encoder_fwd", mutates_args=(), device_types="cuda")
+def transformer_encoder_fwd(x: Tensor, lengths: Optional[Tensor], rng_state: Tensor, params: List[Tensor],
+                            training: bool, dropout: float, eps: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """The post-norm nn.TransformerEncoder stack (4 heads, ReLU) with the key padding mask t >= lengths[b]
+    and the mean over the valid steps (src/encoders.py:99-111, 177-206) on x (B, T, H) = the input
+    projection's output; lengths int64 (B) or None.  -> pooled (B, H), saved (bytes), advanced rng state."""
+    L = _nat.lib()
+    d = _transformer_desc(x, params, training, dropout, eps)
+    dev = x.device
+    saved = torch.empty(max(256, L.mmf_transformer_encoder_saved_bytes(d.batch, d.steps, d.hidden, d.ffn, d.layers)),
+                        dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(256, L.mmf_transformer_encoder_workspace_bytes(d.batch, d.steps, d.hidden, d.ffn, d.layers, 0)),
+                     dtype=torch.uint8, device=dev)
+    pooled = torch.empty(d.batch, d.hidden, dtype=torch.float32, device=dev)
+    rng_next = rng_state.clone()   # snapshot into `saved`, then advanced by the library
+    layers = _transformer_layers([p.data_ptr() for p in params])
+    rc = L.mmf_transformer_encoder_forward(ctypes.byref(d), ctypes.cast(layers, ctypes.c_void_p), x.data_ptr(),
+                                           _nat.ptr(lengths), rng_next.data_ptr(), saved.data_ptr(),
+                                           pooled.data_ptr(), ws.data_ptr(), _nat.stream_ptr(dev))
+    _nat.check(rc, "TransformerSequenceEncoder forward")
+    return pooled, saved, rng_next
+
+
+@transformer_encoder_fwd.register_fake
+def _(x, lengths, rng_state, params, training, dropout, eps):
+    d = _transformer_desc(x, params, training, dropout, eps)
+    nbytes = max(256, _nat.lib().mmf_transformer_encoder_saved_bytes(d.batch, d.steps, d.hidden, d.ffn, d.layers))
+    return x.new_empty(d.batch, d.hidden), x.new_empty(nbytes, dtype=torch.uint8), torch.empty_like(rng_state)
+
+
+@torch.library.custom_op("mmfusion::transformer_encoder_bwd", mutates_args=(), device_types="cuda")
+def transformer_encoder_bwd(x: Tensor, lengths: Optional[Tensor], params: List[Tensor], saved: Tensor,
+                            dpooled: Tensor, training: bool, dropout: float, eps: float,
+                            need_dx: bool) -> List[Tensor]:
+    """-> [dx (empty unless need_dx), then every parameter's gradient in the order of params]."""
+    L = _nat.lib()
+    d = _transformer_desc(x, params, training, dropout, eps)
+    dev = x.device
+    ws = torch.empty(max(256, L.mmf_transformer_encoder_workspace_bytes(d.batch, d.steps, d.hidden, d.ffn, d.layers, 1)),
+                     dtype=torch.uint8, device=dev)
+    dx = torch.empty_like(x) if need_dx else x.new_empty(0)
+    grads = [torch.empty_like(p) for p in params]
+    layers = _transformer_layers([p.data_ptr() for p in params])
+    glayers = _transformer_layers([g.data_ptr() for g in grads])
+    rc = L.mmf_transformer_encoder_backward(ctypes.byref(d), ctypes.cast(layers, ctypes.c_void_p), x.data_ptr(),
+                                            _nat.ptr(lengths), saved.data_ptr(), dpooled.data_ptr(), ws.data_ptr(),
+                                            ctypes.cast(glayers, ctypes.c_void_p), dx.data_ptr() if need_dx else None,
+                                            _nat.stream_ptr(dev))
+    _nat.check(rc, "TransformerSequenceEncoder backward")
+    return [dx] + grads
+
+
+@transformer_encoder_bwd.register_fake
+def _(x, lengths, params, saved, dpooled, training, dropout, eps, need_dx):
+    return [torch.empty_like(x) if need_dx else x.new_empty(0)] + [torch.empty_like(p) for p in params]
+
+
+def _tr_setup(ctx, inputs, output):
+    x, lengths, _rng, params, training, dropout, eps = inputs
+    ctx.set_materialize_grads(False)   # the saved bytes and the rng state reach the backward as None
+    ctx.training, ctx.dropout, ctx.eps = bool(training), float(dropout), float(eps)
+    ctx.has_lengths = lengths is not None
+    ctx.need_dx = bool(x.requires_grad)
+    ctx.save_for_backward(x, lengths if lengths is not None else x.new_empty(0), output[1], *params)
+
+
+def _tr_backward(ctx, dpooled, _dsaved, _drng):
+    if dpooled is None:
+        return None, None, None, None, None, None, None
+    x, lengths, saved, *params = ctx.saved_tensors
+    dx, *grads = torch.ops.mmfusion.transformer_encoder_bwd(
+        x, lengths if ctx.has_lengths else None, list(params), saved, dpooled.contiguous(), ctx.training,
+        ctx.dropout, ctx.eps, ctx.need_dx)
+    return dx if ctx.need_dx else None, None, None, grads, None, None, None
+
+
+transformer_encoder_fwd.register_autograd(_tr_backward, setup_context=_tr_setup)
