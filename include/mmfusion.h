@@ -305,6 +305,58 @@ int mmf_uncertainty_fusion_backward(int32_t batch, int32_t num_modalities, int32
                                     float* duncertainty, void* stream);
 
 /* ---------------------------------------------------------------------
+ * Missing-modality robustness sweep (src/eval.py:312-458 evaluate_missing_modalities) over
+ * HybridFusion: the logits of `num_patterns` 0/1 modality patterns, each constant over the batch
+ * as the reference builds them (src/eval.py:394-404), from ONE shared pass.  Under such a pattern a
+ * masked modality reaches the logits only through constants: its features are zeroed
+ * (src/fusion.py:371-374), as a key every score is -inf and the attended output is exactly
+ * out_proj.bias (src/attention.py:124-140), as a query its aggregate is multiplied by 0
+ * (src/fusion.py:408); P_m and the attended output of every present (q, k) pair are those of the
+ * all-present mask.  So the call runs
+ *   1. the shared pass: mmf_hybrid_forward's own plan for the descriptor in eval mode under the
+ *      all-present mask (at d->matmul_precision), leaving the L-mean of P_m per modality and the
+ *      L-mean attended output per pair as (B, H) fp32 rows -- pooled by one more launch where the
+ *      selected plan keeps (B, L, H) rows;
+ *   2. one tail launch over tiles of (pattern, sample) rows: the aggregate
+ *      mean([Pbar_q] + [present_k ? Abar_{q->k} : b_o(q->k)]) of every present query by SELECTION
+ *      (nothing of an absent modality is read, so a NaN there cannot leak), the gating softmax over
+ *      the present modalities with the reference's fallback (src/fusion.py:462-478), the weighted
+ *      sum and the classifier (layer 1 on the fp32 matrix cores).  fp32 at every matmul-precision
+ *      setting; fixed-order reductions, no float atomics: reruns are bit-identical.
+ * A NaN in a sample's input of a modality that a pattern includes gives that (pattern, sample) row
+ * NaN logits, as the reference does (the forward's ReLU kernels return 0 for a NaN pre-activation,
+ * so the call flags such inputs itself); a pattern without the modality is unaffected, bit for bit.
+ * Only NaN inputs are flagged: a +-Inf input takes the shared pass's arithmetic, where a NaN it
+ * turns into before a ReLU (Inf - Inf in a projection) becomes 0 there, so such a row may come out
+ * finite where the reference gives NaN.  The fusion weights of a flagged row are those of the
+ * shared pass's finite values (the reference's are its fallback weights or NaN): with non-finite
+ * inputs only the logits' NaN is promised.
+ * patterns: HOST array (S, M) of 0 / 1 bytes, read during the call (they travel as kernel
+ * arguments: no host->device copy).  The all-zero pattern is legal: classifier(0), weights 1 / M.
+ * logits_stack (S, B, C); weights_stack (S, B, M), may be NULL.  `saved` is the forward's buffer
+ * (mmf_hybrid_saved_bytes) and `workspace` holds mmf_hybrid_sweep_workspace_bytes(d, S) bytes, both
+ * under the forward's buffer contract (plan_flags, saved_capacity, workspace_capacity).
+ * Checked before anything touches the device: d->training != 0, d->return_attention != 0,
+ * num_patterns < 1, a pattern entry other than 0 / 1, a null argument: MMF_EINVAL; num_patterns >
+ * 1024, classes > 1024 or hidden > 256: MMF_ELIMIT (the size query then returns 0).
+ * Profiling stages: "sweep.shared" (with the forward's stages nested), "sweep.tail".
+ * ------------------------------------------------------------------- */
+size_t mmf_hybrid_sweep_workspace_bytes(const mmf_hybrid_desc* d, int32_t num_patterns);
+int mmf_hybrid_sweep_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* params,
+                             const float* const* x, const uint8_t* patterns, int32_t num_patterns,
+                             void* saved, void* workspace, float* logits_stack, float* weights_stack,
+                             void* stream);
+
+/* Confusion matrices of a stack of logits (stacks, batch, classes) against labels (batch) int64:
+ * pred = the row's argmax with torch.argmax's rule (lowest index among equal maxima; a NaN counts
+ * as the maximum) and counts[s, label, pred] += 1 on device int64 counts (stacks, classes, classes)
+ * that the caller zeroed before the first call.  A label outside [0, classes) is never used as an
+ * index: it adds 1 to bad_labels[0] per stack entry and touches no count.  Integer accumulation
+ * only, so the order cannot change the result.  One launch (confusion_kernel). */
+int mmf_confusion_accumulate(int32_t stacks, int32_t batch, int32_t classes, const float* logits_stack,
+                             const int64_t* labels, int64_t* counts, int64_t* bad_labels, void* stream);
+
+/* ---------------------------------------------------------------------
  * Manifest data path (src/data.py:110-343, MultimodalDataset over .pt shards
  * {columns, data (rows, ncols)}): gather a batch of chunk windows from the
  * HBM-resident shard table into per-modality tensors.

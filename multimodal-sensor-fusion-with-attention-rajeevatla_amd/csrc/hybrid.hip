@@ -1655,4 +1655,140 @@ int mmf_hybrid_train_step(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, 
                                     step_dev, grad_flat, grad_n, stream);
 }
 
+// ---------------------------------------------------------------- missing-modality sweep
+// The sweep's workspace: the all-present mask and the shared pass's own (unused) outputs, the
+// patterns' bit sets, and the L-means the selected plan does not leave as (B, H) rows.
+struct SweepWs {
+  float *ones, *logits0, *fw0;
+  uint32_t *bits, *nan_in;
+  float* Pbar[MMF_MAX_MODALITIES];
+  float* Abar[MMF_MAX_PAIRS];
+};
+
+static void layout_sweep_ws(const HybridPlan& plan, const mmf_hybrid_desc* d, int32_t S, Bump& bp, SweepWs& w) {
+  memset(&w, 0, sizeof(w));
+  const size_t B = d->batch, H = d->hidden, M = d->num_modalities;
+  w.ones = bp.take<float>(B * M);
+  w.logits0 = bp.take<float>(B * d->num_classes);
+  w.fw0 = bp.take<float>(B * M);
+  w.bits = bp.take<uint32_t>(((size_t)S + 3) / 4);
+  w.nan_in = bp.take<uint32_t>(B * M);
+  for (int m = 0; m < d->num_modalities; ++m)
+    if (Lm(d, m) > 1) w.Pbar[m] = bp.take<float>(B * H);
+  for (int g = 0; g < d->num_pairs; ++g)
+    if (!plan.pool && Lm(d, d->pair_q[g]) > 1) w.Abar[g] = bp.take<float>(B * H);
+}
+
+static int check_sweep(const mmf_hybrid_desc* d, int32_t S) {
+  int rc = check_hybrid(d);
+  if (rc) return rc;
+  if (d->training != 0) return fail(MMF_EINVAL, "hybrid_sweep: the sweep is an evaluation (training must be 0)");
+  if (d->return_attention != 0) return fail(MMF_EINVAL, "hybrid_sweep: return_attention is not supported");
+  if (S < 1) return fail(MMF_EINVAL, "hybrid_sweep: num_patterns must be >= 1, got %d", S);
+  if (S > SWEEP_MAX_PATTERNS) return fail(MMF_ELIMIT, "hybrid_sweep: %d patterns > %d", S, SWEEP_MAX_PATTERNS);
+  if (d->num_classes > SWEEP_MAX_CLASSES)
+    return fail(MMF_ELIMIT, "hybrid_sweep: %d classes > %d", d->num_classes, SWEEP_MAX_CLASSES);
+  if (d->hidden > SWEEP_MAX_H) return fail(MMF_ELIMIT, "hybrid_sweep: hidden_dim %d > %d", d->hidden, SWEEP_MAX_H);
+  return MMF_OK;
+}
+
+size_t mmf_hybrid_sweep_workspace_bytes(const mmf_hybrid_desc* d, int32_t num_patterns) {
+  if (check_sweep(d, num_patterns) != MMF_OK) return 0;
+  const HybridPlan plan = resolve_plan(d);
+  Bump bp(nullptr);
+  SweepWs w;
+  layout_sweep_ws(plan, d, num_patterns, bp, w);
+  return bp.off + 256;
+}
+
+int mmf_hybrid_sweep_forward(const mmf_hybrid_desc* d, const mmf_hybrid_params* W, const float* const* x,
+                             const uint8_t* patterns, int32_t num_patterns, void* saved, void* workspace,
+                             float* logits_stack, float* weights_stack, void* stream) {
+  const int32_t S = num_patterns;
+  int rc = check_sweep(d, S);
+  if (rc) return rc;
+  const int M = d->num_modalities, H = d->hidden, np = d->num_pairs;
+  if (!patterns) return fail(MMF_EINVAL, "hybrid_sweep: null patterns");
+  SweepPrepArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  for (int32_t s = 0; s < S; ++s) {
+    uint32_t bits = 0;
+    for (int m = 0; m < M; ++m) {
+      const uint8_t v = patterns[(size_t)s * M + m];
+      if (v > 1) return fail(MMF_EINVAL, "hybrid_sweep: pattern %d, modality %d is %d (entries are 0 or 1)", s, m, (int)v);
+      bits |= (uint32_t)v << m;
+    }
+    pa.words[s >> 2] |= bits << (8 * (s & 3));
+  }
+  if (!W || !x || !saved || !workspace || !logits_stack) return fail(MMF_EINVAL, "hybrid_sweep: null argument");
+  MathScope math_(d->matmul_precision);
+  const HybridPlan plan = resolve_plan(d);
+  Bump bs(saved);
+  Saved s{};
+  layout_saved(plan, d, bs, s);
+  Bump bw(workspace);
+  SweepWs w;
+  layout_sweep_ws(plan, d, S, bw, w);
+  if ((rc = check_buffers(plan, d, bs.off, bw.off))) return rc;
+  pa.ones = w.ones; pa.n_ones = d->batch * M;
+  pa.bits_out = w.bits; pa.n_words = (S + 3) / 4;
+  pa.B = d->batch; pa.M = M; pa.nan_out = w.nan_in;
+  for (int m = 0; m < M; ++m) {
+    if (!x[m]) return fail(MMF_EINVAL, "hybrid_sweep: null input %d", m);
+    pa.x[m] = x[m];
+    pa.xn[m] = (int64_t)Lm(d, m) * d->in_dim[m];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  {
+    // the shared pass: the forward's own plan for this descriptor under the all-present mask, then
+    // the L-means it left unpooled
+    Stage stage_("sweep.shared", st);
+    HIP_TRY(launch_sweep_prep(pa, st));
+    rc = hybrid_forward(plan, d, W, x, w.ones, nullptr, s, w.logits0, w.fw0, nullptr, stream, nullptr);
+    if (rc) return rc;
+    SweepPoolArgs po;
+    memset(&po, 0, sizeof(po));
+    po.B = d->batch; po.H = H;
+    for (int m = 0; m < M; ++m)
+      if (w.Pbar[m]) {
+        // (from the projection GEMM's per-128-row column sums where the plan wrote them: L / 128 rows)
+        po.src[po.nsrc] = s.Pcol[m] ? s.Pcol[m] : s.P[m];
+        po.dst[po.nsrc] = w.Pbar[m];
+        po.L[po.nsrc] = s.Pcol[m] ? Lm(d, m) / 128 : Lm(d, m);
+        po.scale[po.nsrc++] = 1.f / (float)Lm(d, m);
+      }
+    for (int g = 0; g < np; ++g)
+      if (w.Abar[g]) {
+        po.src[po.nsrc] = s.A[g]; po.dst[po.nsrc] = w.Abar[g]; po.L[po.nsrc] = Lm(d, d->pair_q[g]);
+        po.scale[po.nsrc++] = 1.f / (float)Lm(d, d->pair_q[g]);
+      }
+    HIP_TRY(launch_sweep_pool(po, st));
+  }
+  SweepTailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.S = S; ta.B = d->batch; ta.M = M; ta.H = H; ta.C = d->num_classes; ta.npairs = np;
+  ta.bits = reinterpret_cast<const uint8_t*>(w.bits);
+  ta.nan_in = w.nan_in;
+  int cnt[MMF_MAX_MODALITIES];
+  for (int m = 0; m < M; ++m) {
+    ta.Pbar[m] = w.Pbar[m] ? w.Pbar[m] : s.P[m];
+    ta.gate_w[m] = W->gate[m].w;
+    ta.gate_b[m] = W->gate[m].b;
+    cnt[m] = 1;
+  }
+  for (int g = 0; g < np; ++g) {
+    ta.Abar[g] = plan.pool ? s.Ab[g] : (w.Abar[g] ? w.Abar[g] : s.A[g]);
+    ta.bo[g] = W->o[g].b;
+    ta.pq[g] = d->pair_q[g];
+    ta.pk[g] = d->pair_k[g];
+    cnt[d->pair_q[g]]++;
+  }
+  for (int m = 0; m < M; ++m) ta.inv_cnt[m] = 1.0f / (float)cnt[m];
+  ta.W1 = W->cls1.w; ta.b1 = W->cls1.b; ta.W2 = W->cls2.w; ta.b2 = W->cls2.b;
+  ta.logits = logits_stack;
+  ta.weights = weights_stack;
+  STAGE_TRY("sweep.tail", launch_sweep_tail(ta, st));
+  return MMF_OK;
+}
+
 }  // extern "C"

@@ -647,4 +647,59 @@ hipError_t launch_l1_train(const L1Args& a, const L1WgArgs& w, hipStream_t st);
 // workgroups of the one-launch step's forward kernel the device holds at once (occupancy x CUs)
 int l1_train_capacity(bool full_h128);
 
+// ---------------------------------------------------------------------------
+// Missing-modality sweep (sweep.hip; src/eval.py:312-458 evaluate_missing_modalities over
+// HybridFusion): S 0/1 modality patterns, constant over the batch, evaluated from ONE shared pass
+// under the all-present mask.  The shared pass leaves per sample the L-mean of P_m (Pbar_m) and the
+// L-mean attended output of every present pair (Abar_g), (B, H) each; a masked key contributes
+// exactly out_proj.bias, a masked query nothing.  Per (pattern, sample) row the tail kernel builds
+//   agg_q = present_q ? (Pbar_q + sum_{g: q(g) = q} (present_k(g) ? Abar_g : b_o,g)) / n_q : --
+//   weights = compute_adaptive_weights over the present modalities (src/fusion.py:429-479)
+//   fused = sum_{present q} weights_q agg_q;  logits = W2 ReLU(W1 fused + b1) + b2
+// by selection: nothing of an absent modality is read.
+// ---------------------------------------------------------------------------
+constexpr int SWEEP_MAX_PATTERNS = 1024;   // pattern bit sets travel as 1 KB of kernel arguments
+constexpr int SWEEP_MAX_H = 256;
+constexpr int SWEEP_MAX_CLASSES = 1024;
+constexpr int SWEEP_MAX_PAIRS = 56;
+// all-present mask, the pattern bit sets (bit m of byte s = modality m present in pattern s) and,
+// per (sample, modality), whether the input holds a NaN: the forward's ReLU kernels return 0 for a
+// NaN pre-activation, so the shared pass alone would lose what the reference propagates
+struct SweepPrepArgs {
+  float* ones; int32_t n_ones;
+  uint32_t* bits_out; int32_t n_words;
+  int32_t B, M;
+  const float* x[8]; int64_t xn[8];          // inputs (B, xn[m]) flat per sample
+  uint32_t* nan_out;                         // (B, M)
+  uint32_t words[SWEEP_MAX_PATTERNS / 4];
+};
+hipError_t launch_sweep_prep(const SweepPrepArgs& a, hipStream_t st);
+// dst[i] (B, H) = scale[i] * sum over the L[i] rows of src[i] (B, L[i], H), fixed order (an L-mean:
+// the rows themselves with scale 1 / L, or the projection GEMM's per-128-row column sums with
+// L = rows / 128 and scale 1 / rows)
+constexpr int SWEEP_POOL_MAX_SRC = 64;
+struct SweepPoolArgs {
+  int32_t B, H, nsrc;
+  const float* src[SWEEP_POOL_MAX_SRC];
+  float* dst[SWEEP_POOL_MAX_SRC];
+  int32_t L[SWEEP_POOL_MAX_SRC];
+  float scale[SWEEP_POOL_MAX_SRC];
+};
+hipError_t launch_sweep_pool(const SweepPoolArgs& a, hipStream_t st);
+struct SweepTailArgs {
+  int32_t S, B, M, H, C, npairs;
+  const uint8_t* bits;                       // (S) device
+  const uint32_t* nan_in;                    // (B, M): the sample's input of modality m holds a NaN
+  const float* Pbar[8];                      // (B, H)
+  float inv_cnt[8];
+  const float* gate_w[8]; const float* gate_b[8];
+  const float* Abar[SWEEP_MAX_PAIRS];        // (B, H)
+  const float* bo[SWEEP_MAX_PAIRS];          // (H) out_proj.bias of the pair
+  int32_t pq[SWEEP_MAX_PAIRS], pk[SWEEP_MAX_PAIRS];
+  const float *W1, *b1, *W2, *b2;
+  float* logits;                             // (S, B, C)
+  float* weights;                            // (S, B, M) or null
+};
+hipError_t launch_sweep_tail(const SweepTailArgs& a, hipStream_t st);
+
 }  // namespace mmf

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "mmf_conv_encoder_workspace_bytes", "mmf_conv_encoder_forward", "mmf_conv_encoder_backward",
     "mmf_transformer_encoder_saved_bytes", "mmf_transformer_encoder_workspace_bytes",
     "mmf_transformer_encoder_forward", "mmf_transformer_encoder_backward",
+    "mmf_hybrid_sweep_workspace_bytes", "mmf_hybrid_sweep_forward", "mmf_confusion_accumulate",
 )
 
 
@@ -270,6 +271,14 @@ def lib() -> ctypes.CDLL:
     # (desc, layers, x, lengths, saved, dpooled, workspace, layer grads, dx, stream)
     L.mmf_transformer_encoder_backward.argtypes = [POINTER(TransformerDesc), vp] + [vp] * 8
     L.mmf_transformer_encoder_backward.restype = c_int32
+    L.mmf_hybrid_sweep_workspace_bytes.argtypes = [POINTER(HybridDesc), c_int32]
+    L.mmf_hybrid_sweep_workspace_bytes.restype = sz
+    # (desc, params, x, patterns (host), num_patterns, saved, workspace, logits_stack, weights_stack, stream)
+    L.mmf_hybrid_sweep_forward.argtypes = [POINTER(HybridDesc), POINTER(HybridParams), vp, vp, c_int32, vp, vp, vp,
+                                           vp, vp]
+    L.mmf_hybrid_sweep_forward.restype = c_int32
+    L.mmf_confusion_accumulate.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, vp, vp]
+    L.mmf_confusion_accumulate.restype = c_int32
     L.mmf_last_error.argtypes = []
     L.mmf_last_error.restype = ctypes.c_char_p
     L.mmf_version.argtypes = []

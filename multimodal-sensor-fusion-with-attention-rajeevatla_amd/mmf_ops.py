@@ -28,6 +28,8 @@ Operators (csrc entry point, reference interface):
   mc_reduce                        mmf_mc_reduce                     src/uncertainty.py:58-66, 487-491
   temperature_nll                  mmf_temperature_nll               src/uncertainty.py:431-435
   uncertainty_fusion_fwd / _bwd    mmf_uncertainty_fusion_*          src/uncertainty.py:305-362
+  hybrid_mask_sweep                mmf_hybrid_sweep_forward          src/eval.py:377-408 (all subsets, one shared pass)
+  confusion_accumulate             mmf_confusion_accumulate          src/eval.py:408-424 (argmax, counted on the device)
   conv_encoder_fwd / _bwd          mmf_conv_encoder_forward / _backward  src/encoders.py:87-97, 168-175
   transformer_encoder_fwd / _bwd   mmf_transformer_encoder_forward / _backward  src/encoders.py:99-111, 177-206
 """
@@ -1095,6 +1097,70 @@ def _uf_backward(ctx, dfused, _dweights):
 
 
 uncertainty_fusion_fwd.register_autograd(_uf_backward, setup_context=_uf_setup)
+
+
+# ============================================================================ Missing-modality sweep (src/eval.py:312-458)
+@torch.library.custom_op("mmfusion::hybrid_mask_sweep", mutates_args=(), device_types="cuda")
+def hybrid_mask_sweep(idesc: List[int], dropout: float, patterns: List[int], xs: List[Tensor], params: List[Tensor],
+                      return_weights: bool) -> Tuple[Tensor, Tensor]:
+    """-> logits (S, B, C) and fusion weights (S, B, M) (empty unless return_weights) of HybridFusion
+    under S 0/1 modality patterns, each constant over the batch (`patterns`: S * M host integers, row
+    major): one shared pass under the all-present mask, then one tail launch over the (pattern,
+    sample) rows (mmf_hybrid_sweep_forward).  `idesc` is an eval descriptor without attention maps.
+    Inference only: no autograd formula."""
+    L = _nat.lib()
+    # (a copy: the shared descriptor's capacities belong to the forward operators)
+    d = _nat.HybridDesc.from_buffer_copy(hybrid_desc(idesc, dropout))
+    B, M, C, _ = _hybrid_meta(idesc)
+    if M < 1 or len(patterns) % M != 0:
+        raise RuntimeError(f"mmfusion mask sweep: {len(patterns)} pattern entries for {M} modalities")
+    S = len(patterns) // M
+    dev = xs[0].device
+    pat = (ctypes.c_uint8 * max(1, len(patterns)))(*[int(v) & 0xFF if 0 <= int(v) <= 255 else 255 for v in patterns])
+    saved = torch.empty(L.mmf_hybrid_saved_bytes(ctypes.byref(d)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.mmf_hybrid_sweep_workspace_bytes(ctypes.byref(d), S), dtype=torch.uint8, device=dev)
+    d.saved_capacity, d.workspace_capacity = saved.numel(), ws.numel()
+    logits = torch.empty(max(S, 0), B, C, dtype=torch.float32, device=dev)
+    weights = torch.empty((S, B, M) if return_weights else (0,), dtype=torch.float32, device=dev)
+    pstruct = _hybrid_params_struct(params, M, d.num_pairs)
+    xarr = _nat.ptr_array([x.data_ptr() for x in xs])
+    rc = L.mmf_hybrid_sweep_forward(ctypes.byref(d), ctypes.byref(pstruct), ctypes.cast(xarr, ctypes.c_void_p),
+                                    ctypes.cast(pat, ctypes.c_void_p), S, saved.data_ptr(), ws.data_ptr(),
+                                    logits.data_ptr(), weights.data_ptr() if return_weights else None,
+                                    _nat.stream_ptr(dev))
+    _nat.check(rc, "HybridFusion mask sweep")
+    return logits, weights
+
+
+@hybrid_mask_sweep.register_fake
+def _(idesc, dropout, patterns, xs, params, return_weights):
+    B, M, C, _ = _hybrid_meta(idesc)
+    S = len(patterns) // M
+    return xs[0].new_empty(S, B, C), xs[0].new_empty((S, B, M) if return_weights else (0,))
+
+
+@torch.library.custom_op("mmfusion::confusion_accumulate", mutates_args=("counts", "bad_labels"), device_types="cuda")
+def confusion_accumulate(logits_stack: Tensor, labels: Tensor, counts: Tensor, bad_labels: Tensor) -> None:
+    """counts[s, label, argmax(logits_stack[s, b])] += 1 over a (S, B, C) float32 stack and int64 labels
+    (B), into int64 counts (S, C, C); a label outside [0, C) adds to bad_labels (1,) instead
+    (mmf_confusion_accumulate: torch.argmax's tie and NaN rule, integer atomics)."""
+    S, B, C = logits_stack.shape
+    if (logits_stack.dtype != torch.float32 or labels.dtype != torch.int64 or counts.dtype != torch.int64
+            or bad_labels.dtype != torch.int64):
+        raise RuntimeError("mmfusion confusion_accumulate: float32 logits, int64 labels / counts / bad_labels")
+    if tuple(labels.shape) != (B,) or tuple(counts.shape) != (S, C, C) or bad_labels.numel() != 1:
+        raise RuntimeError(f"mmfusion confusion_accumulate: logits {tuple(logits_stack.shape)} need labels ({B},), "
+                           f"counts ({S}, {C}, {C}) and one bad_labels entry")
+    if not (logits_stack.is_contiguous() and labels.is_contiguous() and counts.is_contiguous()):
+        raise RuntimeError("mmfusion confusion_accumulate: contiguous tensors")
+    rc = _nat.lib().mmf_confusion_accumulate(S, B, C, logits_stack.data_ptr(), labels.data_ptr(), counts.data_ptr(),
+                                             bad_labels.data_ptr(), _nat.stream_ptr(logits_stack.device))
+    _nat.check(rc, "confusion accumulate")
+
+
+@confusion_accumulate.register_fake
+def _(logits_stack, labels, counts, bad_labels):
+    return None
 
 
 # ============================================================================ CNN sequence encoder (conv stack)
