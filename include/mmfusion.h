@@ -357,6 +357,51 @@ int mmf_confusion_accumulate(int32_t stacks, int32_t batch, int32_t classes, con
                              const int64_t* labels, int64_t* counts, int64_t* bad_labels, void* stream);
 
 /* ---------------------------------------------------------------------
+ * Standard evaluation (src/eval.py:39-130 evaluate_model and the CalibrationMetrics chain over its
+ * output, src/uncertainty.py:84-192): one batch of logits (batch, classes) fp32 and labels (batch)
+ * int64 into every statistic accuracy / macro-F1 / loss / NLL / ECE / MCE need, accumulated in a
+ * device `state` the caller zeroes once and reads back once after the last batch.
+ *
+ * state: mmf_eval_state_bytes(classes, bins) bytes of 8-byte words (int64 i, float64 f):
+ *   word 0  i  samples (rows with a label in [0, classes))
+ *   word 1  i  correct (pred == label)
+ *   word 2  i  bad labels (rows with a label outside [0, classes))
+ *   word 3  i  calls (with batch > 0)
+ *   word 4  i  rows whose softmax is NaN (a NaN or +inf logit, or every logit -inf)
+ *   word 5  f  sum over calls of the call's mean cross-entropy (src/eval.py:84-86, 104 `loss`:
+ *              the call's sum over its good rows divided by `batch`)
+ *   word 6  f  sum over rows of the cross-entropy (NLL = word 6 / word 0)
+ *   word 7     reserved (stays 0)
+ *   then  i  confusion[label][pred] (classes x classes),
+ *         i  bin_count[bins],  i  bin_correct[bins],  f  bin_confidence_sum[bins].
+ * Per row, with z = logits / *temperature when `temperature` (a device scalar) is given, else the
+ * logits: pred = argmax z by mmf_confusion_accumulate's rule; confidence = 1 / sum exp(z - max z)
+ * in fp32 with a correctly rounded division (equal logits over 2^k classes give exactly 2^-k);
+ * cross-entropy = max z + log sum exp(z - max z) - z[label]; the row's bin is the b with
+ * edges[b] <= confidence < edges[b + 1], the last bin closed (edges: bins + 1 rising fp32 values,
+ * torch.linspace(0, 1, bins + 1) for the reference's bins).  A row with a label outside
+ * [0, classes) adds 1 to word 2 and touches nothing else of the state; its label is never used as
+ * an index.  A row whose softmax is NaN falls in no bin and makes words 5 and 6 NaN, as the
+ * reference chain does.  preds_out (batch) int64 and conf_out (batch) fp32 receive every row's
+ * prediction and confidence; either may be NULL.
+ * Two launches (eval_rows_kernel: one wave per row; eval_reduce_kernel: one workgroup per bin and
+ * one for the totals, over the rows' records in `workspace`), no host synchronisation.  The
+ * confusion counts are 64-bit integer atomics; every float sum is taken in a fixed order by the
+ * one workgroup that owns its state word, so two identical runs leave the same bytes.
+ * Checked before anything touches the device: classes outside 1..1024, bins outside 1..256, batch
+ * outside 0..2^24: MMF_ELIMIT (the size queries then return 0); a null logits / labels / edges /
+ * state / workspace: MMF_EINVAL.  batch == 0 does nothing.
+ * workspace: mmf_eval_workspace_bytes(batch, classes, bins) bytes, 256-byte aligned.
+ * ------------------------------------------------------------------- */
+size_t mmf_eval_state_bytes(int32_t classes, int32_t bins);
+size_t mmf_eval_workspace_bytes(int32_t batch, int32_t classes, int32_t bins);
+int mmf_eval_accumulate(int32_t batch, int32_t classes, int32_t bins, const float* logits,
+                        const int64_t* labels, const float* edges /* bins + 1 */,
+                        const float* temperature /* device scalar or NULL */,
+                        void* state, int64_t* preds_out /* (batch) or NULL */,
+                        float* conf_out /* (batch) or NULL */, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------
  * Manifest data path (src/data.py:110-343, MultimodalDataset over .pt shards
  * {columns, data (rows, ncols)}): gather a batch of chunk windows from the
  * HBM-resident shard table into per-modality tensors.

@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "mmf_transformer_encoder_saved_bytes", "mmf_transformer_encoder_workspace_bytes",
     "mmf_transformer_encoder_forward", "mmf_transformer_encoder_backward",
     "mmf_hybrid_sweep_workspace_bytes", "mmf_hybrid_sweep_forward", "mmf_confusion_accumulate",
+    "mmf_eval_state_bytes", "mmf_eval_workspace_bytes", "mmf_eval_accumulate",
 )
 
 
@@ -279,6 +280,13 @@ def lib() -> ctypes.CDLL:
     L.mmf_hybrid_sweep_forward.restype = c_int32
     L.mmf_confusion_accumulate.argtypes = [c_int32, c_int32, c_int32, vp, vp, vp, vp, vp]
     L.mmf_confusion_accumulate.restype = c_int32
+    L.mmf_eval_state_bytes.argtypes = [c_int32, c_int32]
+    L.mmf_eval_state_bytes.restype = sz
+    L.mmf_eval_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.mmf_eval_workspace_bytes.restype = sz
+    # (batch, classes, bins, logits, labels, edges, temperature, state, preds_out, conf_out, workspace, stream)
+    L.mmf_eval_accumulate.argtypes = [c_int32, c_int32, c_int32] + [vp] * 9
+    L.mmf_eval_accumulate.restype = c_int32
     L.mmf_last_error.argtypes = []
     L.mmf_last_error.restype = ctypes.c_char_p
     L.mmf_version.argtypes = []

@@ -30,6 +30,7 @@ Operators (csrc entry point, reference interface):
   uncertainty_fusion_fwd / _bwd    mmf_uncertainty_fusion_*          src/uncertainty.py:305-362
   hybrid_mask_sweep                mmf_hybrid_sweep_forward          src/eval.py:377-408 (all subsets, one shared pass)
   confusion_accumulate             mmf_confusion_accumulate          src/eval.py:408-424 (argmax, counted on the device)
+  eval_accumulate                  mmf_eval_accumulate               src/eval.py:84-104, src/uncertainty.py:109-129, 191
   conv_encoder_fwd / _bwd          mmf_conv_encoder_forward / _backward  src/encoders.py:87-97, 168-175
   transformer_encoder_fwd / _bwd   mmf_transformer_encoder_forward / _backward  src/encoders.py:99-111, 177-206
 """
@@ -1160,6 +1161,65 @@ def confusion_accumulate(logits_stack: Tensor, labels: Tensor, counts: Tensor, b
 
 @confusion_accumulate.register_fake
 def _(logits_stack, labels, counts, bad_labels):
+    return None
+
+
+# ============================================================================ Standard evaluation (src/eval.py:39-130)
+EVAL_HEAD_WORDS = 8   # include/mmfusion.h: the evaluation state's counters and sums before the confusion matrix
+
+
+def eval_state_words(classes: int, bins: int) -> int:
+    """The evaluation state's length in 8-byte words (mmf_eval_state_bytes / 8)."""
+    return EVAL_HEAD_WORDS + classes * classes + 3 * bins
+
+
+@torch.library.custom_op("mmfusion::eval_accumulate", mutates_args=("state", "preds_out", "conf_out"),
+                         device_types="cuda")
+def eval_accumulate(logits: Tensor, labels: Tensor, edges: Tensor, temperature: Optional[Tensor], state: Tensor,
+                    preds_out: Optional[Tensor], conf_out: Optional[Tensor]) -> None:
+    """One batch of float32 logits (B, C) and int64 labels (B) into the evaluation state (int64 words,
+    include/mmfusion.h's layout, zeroed by the caller): samples / correct / bad labels / calls / NaN
+    rows, the loss and NLL sums, confusion[label, pred] and per bin of the float32 `edges` (bins + 1)
+    the count, correct count and confidence sum; z = logits / temperature with a device scalar.
+    preds_out (B) int64 and conf_out (B) float32 receive the rows' predictions and confidences
+    (mmf_eval_accumulate: two launches, no host read, fixed-order sums)."""
+    if logits.dim() != 2:
+        raise RuntimeError(f"mmfusion eval_accumulate: logits are (B, C), got {tuple(logits.shape)}")
+    B, C = logits.shape
+    bins = edges.numel() - 1
+    if (logits.dtype != torch.float32 or labels.dtype != torch.int64 or edges.dtype != torch.float32
+            or state.dtype != torch.int64 or (temperature is not None and temperature.dtype != torch.float32)
+            or (preds_out is not None and preds_out.dtype != torch.int64)
+            or (conf_out is not None and conf_out.dtype != torch.float32)):
+        raise RuntimeError("mmfusion eval_accumulate: float32 logits / edges / temperature / conf_out, int64 labels / "
+                           "state / preds_out")
+    if (tuple(labels.shape) != (B,) or edges.dim() != 1 or (temperature is not None and temperature.numel() != 1)
+            or (preds_out is not None and tuple(preds_out.shape) != (B,))
+            or (conf_out is not None and tuple(conf_out.shape) != (B,))):
+        raise RuntimeError(f"mmfusion eval_accumulate: logits {tuple(logits.shape)} need labels / preds_out / conf_out "
+                           f"({B},), 1-D edges and a one-element temperature")
+    L = _nat.lib()
+    need = L.mmf_eval_state_bytes(C, bins)
+    if need == 0:
+        _nat.check(2, "eval accumulate")
+    if state.dim() != 1 or state.numel() * 8 != need:
+        raise RuntimeError(f"mmfusion eval_accumulate: the state of {C} classes and {bins} bins is {need // 8} int64 "
+                           f"words, got {tuple(state.shape)}")
+    tensors = [logits, labels, edges, state] + [t for t in (temperature, preds_out, conf_out) if t is not None]
+    if not all(t.is_contiguous() for t in tensors):
+        raise RuntimeError("mmfusion eval_accumulate: contiguous tensors")
+    dev = logits.device
+    if any(t.device != dev for t in tensors):
+        raise RuntimeError("mmfusion eval_accumulate: every tensor on the logits' device")
+    ws = torch.empty(max(256, L.mmf_eval_workspace_bytes(B, C, bins)), dtype=torch.uint8, device=dev)
+    rc = L.mmf_eval_accumulate(B, C, bins, logits.data_ptr(), labels.data_ptr(), edges.data_ptr(), _nat.ptr(temperature),
+                               state.data_ptr(), _nat.ptr(preds_out), _nat.ptr(conf_out), ws.data_ptr(),
+                               _nat.stream_ptr(dev))
+    _nat.check(rc, "eval accumulate")
+
+
+@eval_accumulate.register_fake
+def _(logits, labels, edges, temperature, state, preds_out, conf_out):
     return None
 
 
