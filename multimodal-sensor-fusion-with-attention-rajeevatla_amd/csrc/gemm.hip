@@ -368,20 +368,60 @@ __device__ __forceinline__ void stage_tile(float* lds, const Operand& op, int64_
   }
 }
 
+// The same addresses with the per-tile part taken out (gemm_lds_body's steady state): for a source
+// with row_div == 1 and a tile that lies wholly inside [k0, kend), stage_tile's source address is a
+// wave-uniform pointer that moves by a fixed step per k-tile (RK: DK floats from ptr + boff + e0 ld;
+// KR: DK rows from ptr + boff) plus a per-lane byte offset that depends on the source only.  The
+// offsets are computed once per source (stage_lane_off), the pointer is advanced on the scalar unit,
+// and the DMA takes the SGPR-base form of global_load_lds: no clamp, no 64-bit VALU address and no
+// row_div test per tile.  Callers check stage_src_fast first; it bounds the offsets to 32 bits.
+// (stage_lane_off's KR term eext - 4 is never negative: launch_gemm sends only KR extents that are
+// multiples of 4, hence >= 4, to this kernel; stage_src_fast asks for it again, next to the cast.)
+__device__ __forceinline__ bool stage_src_fast(const Operand& op, int eext) {
+  return op.row_div == 1 && op.ld <= (1 << 22) && eext >= 4 && eext <= (1 << 22);
+}
+template <int MODE, int DK>
+__device__ __forceinline__ uint32_t stage_lane_off(const Operand& op, int e0, int eext, int ins, int lane) {
+  constexpr int S = DK / 4;
+  if (MODE == MODE_RK) {
+    const int row = ins * (64 / S) + lane / S;
+    const int slot = (lane % S) ^ swz<DK>(row);
+    const int e = min(e0 + row, eext - 1);
+    return 4u * (uint32_t)((e - e0) * op.ld + 4 * slot);
+  } else {
+    const int e = min(e0 + 4 * (lane & 31), eext - 4);
+    return 4u * (uint32_t)((ins * 2 + (lane >> 5)) * op.ld + e);
+  }
+}
+template <int MODE>
+__device__ __forceinline__ const char* stage_src_base(const Operand& op, int64_t boff, int e0, int k0) {
+  const int64_t first = MODE == MODE_RK ? (int64_t)e0 * op.ld + k0 : (int64_t)k0 * op.ld;
+  return reinterpret_cast<const char*>(op.ptr + boff + first);
+}
+template <int MODE, int DK>
+__device__ __forceinline__ int stage_src_step(const Operand& op) {   // bytes per k-tile
+  return MODE == MODE_RK ? 4 * DK : 4 * DK * op.ld;
+}
+
 // Zero the k >= kv part of a staged tile (last tile of a contraction; kv % 4 == 0 for RK).
 template <int MODE, int DK>
 __device__ __forceinline__ void zero_tail(float* lds, int kv) {
   const int t = threadIdx.x;
+  // A register-budget workaround, not a need of this function: the barrier makes the four zeros here,
+  // on the cold path.  Hoisted, they hold 4 VGPRs across the whole k-loop and
+  // gemm_lds_chain_kernel<0, 1, 16, 3, *> (capped at 168 VGPRs) spills one.  Compiler dependent:
+  // after a toolchain change re-check those three kernels for scratch.
+  f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+  asm volatile("" : "+v"(zero));
   if (MODE == MODE_RK) {
     constexpr int S = DK / 4;
     for (int idx = t; idx < BM * S; idx += NT) {
       const int row = idx / S, slot = idx % S;
-      if (4 * slot >= kv)
-        *reinterpret_cast<f32x4*>(lds + row * DK + ((slot ^ swz<DK>(row)) << 2)) = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (4 * slot >= kv) *reinterpret_cast<f32x4*>(lds + row * DK + ((slot ^ swz<DK>(row)) << 2)) = zero;
     }
   } else {
     for (int idx = t; idx < DK * BM / 4; idx += NT) {
-      if (idx / (BM / 4) >= kv) *reinterpret_cast<f32x4*>(lds + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (idx / (BM / 4) >= kv) *reinterpret_cast<f32x4*>(lds + idx * 4) = zero;
     }
   }
 }
@@ -557,33 +597,81 @@ __device__ __forceinline__ void gemm_lds_body(const GemmArgs& args) {
   const bool want_db = partial && T.part_db != nullptr && T.j0 == 0;
   float dbsum = 0.f;
 
+  // the cursor's kernel-argument words, read once per tile (a source switch still reads its K)
+  const int src_count = G.src_count, src_begin = G.src_begin;
+  const int kfirst = partial ? T.split * G.kchunk : 0, kchunk = G.kchunk;
   auto first_from = [&](int si) {
     KCursor k;
-    for (k.si = si; k.si < G.src_count; ++k.si) {
-      const GemmSrc& S = args.s[G.src_begin + k.si];
-      k.k0 = partial ? T.split * G.kchunk : 0;
-      k.kend = partial ? min(S.K, k.k0 + G.kchunk) : S.K;
+    for (k.si = si; k.si < src_count; ++k.si) {
+      const GemmSrc& S = args.s[src_begin + k.si];
+      k.k0 = kfirst;
+      k.kend = partial ? min(S.K, k.k0 + kchunk) : S.K;
       if (k.k0 < k.kend) break;
     }
     return k;
   };
   auto advance = [&](KCursor k) {
-    if (k.si >= G.src_count) return k;
+    if (k.si >= src_count) return k;
     k.k0 += DK;
     if (k.k0 < k.kend) return k;
     return first_from(k.si + 1);
   };
-  // the staged source's operands, re-read from the kernel arguments only when
-  // the cursor moves to another source
-  Operand opA = args.s[G.src_begin].a, opB = args.s[G.src_begin].b;
-  int op_si = 0;
   // per-segment operands (seg_stride != 0): offset by the segment of the tile's first row
   const int64_t seg = G.seg_rows > 0 ? T.i0 / G.seg_rows : 0;
+  // The staged source (fp32 forms): what stage_tile's addresses keep from tile to tile -- see
+  // stage_src_fast.  src_a / src_b point at the next tile to issue, off_a / off_b are the lane
+  // offsets of the wave's DMA pieces.  Set when the cursor moves to another source (or starts
+  // inside one: the prologue), advanced with every tile issued from it.
+  constexpr int PW = B16 ? 1 : BM * DK / 256 / 4;   // DMA pieces per wave and operand tile
+  const int uwave = __builtin_amdgcn_readfirstlane(wave);
+  int op_si = -1;
+  bool src_fast = false;
+  const char* src_a = nullptr;
+  const char* src_b = nullptr;
+  int step_a = 0, step_b = 0;
+  uint32_t off_a[PW], off_b[PW];
+  // a whole tile of the staged source: PW DMAs per operand from the running pointers
+  auto stage_fast = [&](int buf) {
+    float* At = lds + buf * SSTRIDE + uwave * PW * 256;
+#pragma unroll
+    for (int u = 0; u < PW; ++u)
+      __builtin_amdgcn_global_load_lds((const void*)(src_a + off_a[u]),
+                                       (__attribute__((address_space(3))) void*)(At + u * 256), 16, 0, 0);
+#pragma unroll
+    for (int u = 0; u < PW; ++u)
+      __builtin_amdgcn_global_load_lds((const void*)(src_b + off_b[u]),
+                                       (__attribute__((address_space(3))) void*)(At + DTILE + u * 256), 16, 0, 0);
+    src_a += step_a;
+    src_b += step_b;
+  };
+  // any tile: a source switch, a partial last tile, a row_div operand, the bf16-operand forms
   auto stage = [&](int buf, const KCursor& k) {
-    if (k.si != op_si) {
-      opA = args.s[G.src_begin + k.si].a;
-      opB = args.s[G.src_begin + k.si].b;
-      op_si = k.si;
+    const Operand& opA = args.s[src_begin + k.si].a;
+    const Operand& opB = args.s[src_begin + k.si].b;
+    if constexpr (!B16) {
+      if (k.si != op_si) {
+        op_si = k.si;
+        src_fast = stage_src_fast(opA, G.M) && stage_src_fast(opB, G.N);
+        if (src_fast) {
+          src_a = stage_src_base<AMODE>(opA, offA + seg * opA.seg_stride, T.i0, k.k0);
+          src_b = stage_src_base<BMODE>(opB, offB + seg * opB.seg_stride, T.j0, k.k0);
+          step_a = stage_src_step<AMODE, DK>(opA);
+          step_b = stage_src_step<BMODE, DK>(opB);
+#pragma unroll
+          for (int u = 0; u < PW; ++u) {
+            off_a[u] = stage_lane_off<AMODE, DK>(opA, T.i0, G.M, uwave * PW + u, lane);
+            off_b[u] = stage_lane_off<BMODE, DK>(opB, T.j0, G.N, uwave * PW + u, lane);
+          }
+        }
+      }
+      if (src_fast) {
+        if (k.k0 + DK <= k.kend) {
+          stage_fast(buf);
+          return;
+        }
+        src_a += step_a;   // (a partial tile is a source's last; kept in step all the same)
+        src_b += step_b;
+      }
     }
     float* At = lds + buf * SSTRIDE;
     if constexpr (B16) {
@@ -601,11 +689,14 @@ __device__ __forceinline__ void gemm_lds_body(const GemmArgs& args) {
                          wave, lane);
       }
     } else {
-      stage_tile<AMODE, DK>(At, opA, offA + seg * opA.seg_stride, T.i0, G.M, k.k0, k.kend, wave, lane);
-      stage_tile<BMODE, DK>(At + DTILE, opB, offB + seg * opB.seg_stride, T.j0, G.N, k.k0, k.kend, wave, lane);
+      stage_tile<AMODE, DK>(At, opA, offA + seg * opA.seg_stride, T.i0, G.M, k.k0, k.kend, uwave, lane);
+      stage_tile<BMODE, DK>(At + DTILE, opB, offB + seg * opB.seg_stride, T.j0, G.N, k.k0, k.kend, uwave, lane);
     }
   };
-  // wait until at most `ahead` tiles' DMAs are outstanding (vmcnt needs an immediate)
+  // wait until at most `ahead` tiles' DMAs are outstanding (vmcnt needs an immediate).  The counts
+  // assume that a wave's only VM operations between the prologue and the last k-tile are its
+  // DMA_PER_TILE DMAs per tile: a global load or store added inside the k-loop would be counted in
+  // their place and the wait would let a tile through that has not landed.
   auto wait_tiles = [&](int ahead) {
     if (ahead <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_TILE) : "memory");
@@ -614,15 +705,22 @@ __device__ __forceinline__ void gemm_lds_body(const GemmArgs& args) {
   };
   static_assert(NSTAGE >= 2 && NSTAGE <= 5, "ring depth");
 
-  KCursor cur = first_from(0);
-  if (cur.si < G.src_count) {
+  // One cursor, the issuing one.  The consuming side needs only each tile's valid depth, which the
+  // issue leaves in kvq (kvq[q]: tile `tile + q`), and ends when no issued tile is left.
+  KCursor iss = first_from(0);
+  if (iss.si < src_count) {
+    int kvq[NSTAGE] = {};
     // prologue: NSTAGE-1 tiles in flight; tile n always lives in buffer n % NSTAGE
-    KCursor iss = cur;
-    int nissued = 0;
-    for (int q = 0; q < NSTAGE - 1 && iss.si < G.src_count; ++q) {
-      stage(q, iss);
-      iss = advance(iss);
-      ++nissued;
+    int nissued = 0, ibuf = 0;
+#pragma unroll
+    for (int q = 0; q < NSTAGE - 1; ++q) {
+      if (iss.si < src_count) {
+        stage(q, iss);
+        kvq[q] = iss.kend - iss.k0;
+        iss = advance(iss);
+        ++nissued;
+        ibuf = q + 1;
+      }
     }
     int tile = 0, buf = 0;
     for (;;) {
@@ -632,7 +730,11 @@ __device__ __forceinline__ void gemm_lds_body(const GemmArgs& args) {
       lds_barrier();
       float* At = lds + buf * SSTRIDE;
       float* Bt = At + DTILE;
-      const int kv = cur.kend - cur.k0;
+      const int kv = kvq[0];
+      // the tile to issue in this round (into buffer ibuf = nissued % NSTAGE): `hot` when it is a
+      // whole tile of the staged source, which the fp32 form issues between its MFMAs below
+      const bool more = iss.si < src_count;
+      const bool hot = !B16 && more && src_fast && iss.si == op_si && iss.k0 + DK <= iss.kend;
       if (kv < DK) {
         if constexpr (B16) {
           if constexpr (AMODE == MODE_KR) zero_tail_b16_kr(At, kv);
@@ -648,11 +750,9 @@ __device__ __forceinline__ void gemm_lds_body(const GemmArgs& args) {
         }
         lds_barrier();
       }
-      if (iss.si < G.src_count) {
-        stage(nissued % NSTAGE, iss);
-        iss = advance(iss);
-        ++nissued;
-      }
+      // (the buffer restaged was last read in the previous round, and every wave is past this
+      // round's barrier: any point from here on is safe for the DMA)
+      if (more && (!hot || BF != 0)) stage(ibuf, iss);
       if (B16 && AMODE == MODE_KR && want_db) {
         // bias grad of a TN dW from the bf16 A image (thread: row t&127, k half t>>7)
         const int row = t & (BM - 1), kh = t >> 7;
@@ -715,24 +815,37 @@ if constexpr (B16) {
         }
       } else {
 #pragma unroll
-      for (int j = 0; j < DK / 8; ++j) {
-        f32x4 af[2], bf[2];
+        for (int j = 0; j < DK / 8; ++j) {
+          f32x4 af[2], bf[2];
 #pragma unroll
-        for (int a = 0; a < 2; ++a) af[a] = frag<AMODE, DK>(At, wm * 64 + a * 32 + c, j, h);
+          for (int a = 0; a < 2; ++a) af[a] = frag<AMODE, DK>(At, wm * 64 + a * 32 + c, j, h);
 #pragma unroll
-        for (int b = 0; b < 2; ++b) bf[b] = frag<BMODE, DK>(Bt, wn * 64 + b * 32 + c, j, h);
+          for (int b = 0; b < 2; ++b) bf[b] = frag<BMODE, DK>(Bt, wn * 64 + b * 32 + c, j, h);
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+          for (int s = 0; s < 4; ++s) {
 #pragma unroll
-          for (int a = 0; a < 2; ++a)
+            for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = mfma32(af[a][s], bf[b][s], acc[a][b]);
+              for (int b = 0; b < 2; ++b) acc[a][b] = mfma32(af[a][s], bf[b][s], acc[a][b]);
+            if (j == 0 && s == 0) {
+              // the next tile's DMA under the first MFMAs: scalar pointer steps and 2 PW DMAs
+              __builtin_amdgcn_sched_barrier(0);
+              if (hot) stage_fast(ibuf);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+        }
       }
+      // this round's issue, booked (the cursor's source switch may load: after the MFMAs)
+      if (more) {
+        kvq[NSTAGE - 1] = iss.kend - iss.k0;
+        iss = advance(iss);
+        ++nissued;
+        ibuf = ibuf == NSTAGE - 1 ? 0 : ibuf + 1;
       }
-      const KCursor nx = advance(cur);
-      if (nx.si >= G.src_count) break;
-      cur = nx;
-      ++tile;
+      if (++tile == nissued) break;
+#pragma unroll
+      for (int q = 0; q < NSTAGE - 1; ++q) kvq[q] = kvq[q + 1];
       buf = buf == NSTAGE - 1 ? 0 : buf + 1;
     }
   }
